@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: query-slices/sec (512x512), end-to-end ProtoSAM inference (BASELINE.json).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
       N > 1 without a launcher: this process stays off the GPU and starts N fresh ranks itself
       (python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py ...),
       relays rank 0's JSON line and exits with the ranks' status. Under a launcher (WORLD_SIZE in the
@@ -16,8 +16,8 @@ Support features / prototype banks are cached per z-part (values identical to th
 SURVEY Q18); the line also carries the reference-shaped numbers: `per_slice_forward` (one `ProtoSAM.forward` per slice, what
 validation_protosam.py:387 does) and `no_support_cache` (support re-encoded for every slice, grid_proto_fewshot.py:181-184).
 
-Prints ONE JSON line on rank 0, with `roofline` (dominant kernel = the MFMA GEMM, timed live with HIP events on its own
-stream), `roofline_hbm` (the HBM-bound kernels: achieved algorithmic GB/s), per-stage times, and `cpu_baseline` (the CPU
+Prints ONE JSON line on rank 0, with `ms_per_step` (wall time of one of the K timed steps), `roofline` (dominant kernel = the
+MFMA GEMM, timed live with HIP events on its own stream), `roofline_hbm` (the HBM-bound kernels: achieved algorithmic GB/s), per-stage times, and `cpu_baseline` (the CPU
 oracle on a bounded sample of the same workload, timed on this host's cores at all cores and at 1 thread).
 """
 import argparse
@@ -67,7 +67,12 @@ def parse_args(argv=None):
                     "a step is ONE pass over the --slices volume, rank r takes z = r (mod world) (SURVEY 8e), one all-gather per step")
     ap.add_argument("--no-other-configs", action="store_true", help="skip the BASELINE configs 2 / 3 / 5 legs of the default run")
     ap.add_argument("--cpu-sam-depth", type=int, default=None, help="debug: truncate both models' SAM depth")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step "
+                    "returned as DIR/<name>.npy (see dump_outputs)")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def step_slices(s, parts, B, world, rank):
@@ -89,6 +94,31 @@ def step_slices(s, parts, B, world, rank):
 def strong_slices(n_slices, world, rank):
     """--scaling strong: the slices of the whole volume rank `rank` owns, z = rank (mod world) (protosam_amd.runner.shard_slices)."""
     return list(range(rank, n_slices, world))
+
+
+DUMP_MAX_BYTES = 64 << 20      # --dump-outputs: all files together
+
+
+def dump_outputs(out_dir, masks, zs, n_prompts):
+    """--dump-outputs: what the last timed step handed its caller, as .npy files in `out_dir`: `masks` [n, S, S] float32 (the step's
+    uint8 masks, every rank's rows in all-gather order), `n_prompts` [n] float64 (prompt sets per slice, the step's per-slice stats),
+    `slice_z` [n] float64 (the volume slice of each row) and `rows` [n] float64 (each row's position in the step). Inputs and weights
+    are seeded, so two builds run with the same arguments can be compared array by array. When the step's rows would exceed
+    DUMP_MAX_BYTES, a fixed seeded sample of them is written. Returns {name: shape}."""
+    import numpy as np
+    import torch
+    n = masks.shape[0]
+    row_bytes = masks[0].numel() * 4 + 3 * 8
+    keep = max(1, (DUMP_MAX_BYTES - 4096) // row_bytes)          # (4096: room for the four .npy headers)
+    rows = np.arange(n) if n <= keep else np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+    arrays = {"masks": masks.index_select(0, torch.as_tensor(rows, device=masks.device)).cpu().numpy().astype(np.float32),
+              "n_prompts": np.asarray(n_prompts, dtype=np.float64)[rows],
+              "slice_z": np.asarray(zs, dtype=np.float64)[rows],
+              "rows": rows.astype(np.float64)}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
 
 
 def launch_ranks(args):
@@ -367,6 +397,16 @@ def main(argv=None, runtime=None):
         per_rank_ms = [round(float(v) / args.steps * 1e3, 3) for v in every[:, 0]]
         allgather_ms = [round(float(v) * 1e3, 3) for v in every[:, 1]]
         elapsed = float(every[:, 0].max())
+    if args.dump_outputs:
+        # outside the timed region and before any later leg reuses `out`: every rank's (z, prompt sets) of the last timed step, in
+        # the row order of the gathered masks
+        meta = torch.tensor([zs, st], dtype=torch.int64, device=dev).t().contiguous()
+        if world > 1:
+            meta = all_gather_rows(meta)
+        if rank == 0:
+            meta = meta.cpu()
+            shapes = dump_outputs(args.dump_outputs, full, meta[:, 0].tolist(), meta[:, 1].tolist())
+            log(f"dumped the last timed step to {args.dump_outputs}: {shapes}")
 
     if rank != 0:
         if world > 1:

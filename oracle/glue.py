@@ -291,7 +291,7 @@ def protosam_forward(query_image, output_logits, sam_sd, sam_type="vit_b", use_b
     if features is None:
         features = oenc.image_encoder(sam_preprocess(img_u8), sam_sd, model_type=sam_type, depth=encoder_depth)
     if taps is not None:
-        taps.update(bboxes=bboxes, points=points, img_u8=img_u8, features=features, low_res=[], masks=[])
+        taps.update(bboxes=bboxes, points=points, img_u8=img_u8, features=features, low_res=[], masks=[], mask_channel=[])
     masks, scores = [], []
     if use_mask and not (use_points or use_bbox):                                          # :468-498, 664-665
         for in_mask in mask_prompts(cc):
@@ -303,6 +303,7 @@ def protosam_forward(query_image, output_logits, sam_sd, sam_type="vit_b", use_b
             if taps is not None:
                 taps["low_res"].append(low)
                 taps["masks"].append(m[k].numpy())
+                taps["mask_channel"].append(k)
         points, bboxes = [], []
     negs = sam_neg_points(cc, output_p) if (use_neg_points and use_points) else [None] * len(points)
     if taps is not None:
@@ -320,6 +321,7 @@ def protosam_forward(query_image, output_logits, sam_sd, sam_type="vit_b", use_b
         if taps is not None:
             taps["low_res"].append(low)
             taps["masks"].append(m[0].numpy())
+            taps["mask_channel"].append(0)
     pred = torch.tensor(sum(masks) > 0).float()                                            # :669-672
     pred = F.interpolate(pred[None, None], size=original_size, mode="nearest")[0][0]       # :676
     return pred, scores

@@ -209,24 +209,46 @@ def _unpack(bits, shape):
     return np.unpackbits(bits)[:shape[0] * shape[1]].reshape(shape).astype(bool)
 
 
+ROUNDING_LOGIT = 1e-5
+
+
+def _assert_mask_equal(pred, ref, taps):
+    """The final mask bit for bit on every pixel fp32 decides. The mask is the union over prompt sets of (up-sampled logit > 0),
+    sampled by the nearest resize to ORCH_SIZE (ProtoSAM.py:669-676). Where the largest of those logits lies within ROUNDING_LOGIT
+    of zero, the CPU's vector width alone can flip the pixel: AVX-512 and AVX2 kernels give image features 3e-6 and low-res logits
+    6e-6 apart (bilinear up-sampling cannot widen that), and the reference's record was written on one CPU. Such pixels are excused;
+    there are 0 ... 5 of 262144 per case."""
+    from oracle import sam_prompt_decoder as odec
+    from protosam_amd import synth_cases as gi
+    up = torch.stack([odec.postprocess_masks(torch.as_tensor(low)[None], (1024, 1024), (1024, 1024), "batched")[0, c]
+                      for low, c in zip(taps["low_res"], taps["mask_channel"])])
+    step = 1024 // gi.ORCH_SIZE
+    open_ = (up.max(dim=0).values[::step, ::step].abs() <= ROUNDING_LOGIT).numpy()
+    got = pred.numpy().astype(bool)
+    assert np.array_equal(got[~open_], ref[~open_]), int((got != ref)[~open_].sum())
+    assert int(open_.sum()) <= 8, int(open_.sum())
+
+
 @pytest.mark.parametrize("name", ["default", "cca", "conf_pts", "centroid_box", "box_only", "mask", "mask_cca", "neg"])
 def test_protosam_forward_vs_reference_record(gold, orch, name):
     """oracle/glue.protosam_forward == the reference's ProtoSAM.forward (models/ProtoSAM.py:536-678) run on CPU in the build
-    container for every flag set: final mask bit for bit, scores to 1e-5."""
+    container for every flag set: final mask bit for bit (up to fp32 rounding, _assert_mask_equal), scores to 1e-5."""
     from oracle import glue
     from protosam_amd import synth_cases as gi
     kw = gi.ORCH_FLAGS[name]
+    taps = {}
     with torch.no_grad():
         pred, scores = glue.protosam_forward(orch["q"], gi.orch_coarse_logits(), orch["sd"], "vit_b", postprocess="batched",
-                                             encoder_depth=gi.ORCH_SAM_DEPTH, features=orch["feats"], **kw)
+                                             encoder_depth=gi.ORCH_SAM_DEPTH, features=orch["feats"], taps=taps, **kw)
     ref = _unpack(gold[f"orch_{name}_mask"], (gi.ORCH_SIZE, gi.ORCH_SIZE))
-    assert np.array_equal(pred.numpy().astype(bool), ref)
+    _assert_mask_equal(pred, ref, taps)
     np.testing.assert_allclose(np.array(scores, dtype=np.float64), gold[f"orch_{name}_scores"], atol=1e-5, rtol=0)
 
 
 @pytest.mark.parametrize("name,k", [("default", 3), ("conf_pts", 3), ("cca", 2)])
 def test_protosam_num_points_vs_reference_record(orch, name, k):
-    """num_points_for_sam = k > 1 (ProtoSAM.py:266-289,376-387): oracle == the reference's recorded run, mask bit for bit."""
+    """num_points_for_sam = k > 1 (ProtoSAM.py:266-289,376-387): oracle == the reference's recorded run, mask bit for bit (up to
+    fp32 rounding, _assert_mask_equal)."""
     import os
     from oracle import glue
     from protosam_amd import synth_cases as gi
@@ -236,7 +258,7 @@ def test_protosam_num_points_vs_reference_record(orch, name, k):
         pred, scores = glue.protosam_forward(orch["q"], gi.orch_coarse_logits(), orch["sd"], "vit_b", postprocess="batched",
                                              encoder_depth=gi.ORCH_SAM_DEPTH, features=orch["feats"], taps=taps, num_points=k,
                                              **gi.ORCH_FLAGS[name])
-    assert np.array_equal(pred.numpy().astype(bool), _unpack(rec[f"orch_{name}_k{k}_mask"], (gi.ORCH_SIZE, gi.ORCH_SIZE)))
+    _assert_mask_equal(pred, _unpack(rec[f"orch_{name}_k{k}_mask"], (gi.ORCH_SIZE, gi.ORCH_SIZE)), taps)
     np.testing.assert_allclose(np.array(scores, dtype=np.float64), rec[f"orch_{name}_k{k}_scores"], atol=1e-5, rtol=0)
     assert np.array_equal(np.stack([np.asarray(p) for p in taps["points"]]).astype(np.int32), rec[f"orch_{name}_k{k}_points"])
 

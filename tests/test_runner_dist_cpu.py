@@ -224,15 +224,17 @@ def _bench_main_worker(rank, world, port, argv, q):
 
 
 @pytest.mark.parametrize("scaling", ["weak", "strong"])
-def test_bench_main_rank_body_world2(scaling):
+def test_bench_main_rank_body_world2(scaling, tmp_path):
     """bench.main()'s rank body - everything between the launcher and the JSON line - at world 2 under gloo with a stubbed `run_slices`
     (bench.DeviceRuntime -> HostRuntime): argument handling, the all-gather of rank ids, warm-up, the timed loop with the event pairs
-    around the all-gather, the per-rank reductions, rank 0's line and the teardown. What the first real 8-GPU run can then still find
-    is RCCL and the kernels, not bench.py."""
+    around the all-gather, the per-rank reductions, rank 0's line, `--dump-outputs` of the gathered last step and the teardown. What
+    the first real 8-GPU run can then still find is RCCL and the kernels, not bench.py."""
+    import numpy as np
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     port = _free_port()
-    argv = ["--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "4", "--micro", "4", "--slices", "24", "--scaling", scaling]
+    argv = ["--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "4", "--micro", "4", "--slices", "24", "--scaling", scaling,
+            "--dump-outputs", str(tmp_path / "dump")]
     procs = [ctx.Process(target=_bench_main_worker, args=(r, 2, port, argv, q)) for r in range(2)]
     for p in procs:
         p.start()
@@ -252,3 +254,54 @@ def test_bench_main_rank_body_world2(scaling):
     assert abs(max(line["per_rank_ms_per_step"]) - line["ms_per_step"]) < 1e-2
     assert abs(line["value"] * line["ms_per_step"] * 1e-3 - 2 * B) < 1e-2 * 2 * B          # whole-job slices per step / max-over-ranks time
     assert line["cpu_baseline"] is None and "per_slice_forward" not in line and line["config"]["slices_per_step_per_gpu"] == B
+    dump = {n: np.load(tmp_path / "dump" / f"{n}.npy") for n in ("masks", "n_prompts", "slice_z", "rows")}
+    assert dump["slice_z"].tolist() == zs0 + zs1 and dump["rows"].tolist() == list(range(2 * B))       # rank-major, as gathered
+    assert dump["n_prompts"].tolist() == [1 + (z % 2) for z in zs0 + zs1]
+    assert dump["masks"].dtype == np.float32 and dump["masks"].shape == (2 * B, 512, 512)
+    assert all(np.array_equal(dump["masks"][i], _fake_mask512(z).numpy()) for i, z in enumerate(zs0 + zs1))
+
+
+class _CountingRuntime(HostRuntime):
+    def __init__(self):
+        self.step_calls = 0
+
+    def run_slices(self, model, vol, sup_imgs, sup_masks, zs, dev, out=None, batch=1):
+        self.step_calls += out is not None          # (bench.py's steps pass their output buffer, its setup calls do not)
+        return super().run_slices(model, vol, sup_imgs, sup_masks, zs, dev, out=out, batch=batch)
+
+
+def test_bench_dump_outputs_world1(tmp_path, monkeypatch):
+    """`bench.py --dump-outputs DIR` at world 1: `--steps` timed steps after `--warmup`, the last one's masks / prompt sets / slices
+    written as float arrays, the same files from two runs with the same arguments, and a fixed sample of rows (64 MB in all at most)
+    when the step returns more."""
+    import numpy as np
+    import bench
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+        monkeypatch.delenv(k, raising=False)
+    names = ("masks", "n_prompts", "slice_z", "rows")
+    argv = ["--steps", "5", "--warmup", "2", "--batch", "4", "--micro", "4", "--slices", "24", "--no-extras", "--no-cpu-baseline"]
+    runs = []
+    for i in range(2):
+        rt = _CountingRuntime()
+        r = bench.main(argv + ["--dump-outputs", str(tmp_path / f"run{i}")], runtime=rt)
+        assert rt.step_calls == 2 + 5 and r["line"]["steps"] == 5 and r["line"]["ms_per_step"] > 0
+        runs.append({n: np.load(tmp_path / f"run{i}" / f"{n}.npy") for n in names})
+    from protosam_amd.runner import part_assign
+    a = runs[0]
+    parts = [[z for z in range(24) if part_assign(z, 24) == pt] for pt in range(3)]
+    assert a["slice_z"].tolist() == r["last_zs"] == bench.step_slices(2 + 4, parts, 4, 1, 0)
+    assert a["n_prompts"].tolist() == [1 + (z % 2) for z in r["last_zs"]] and a["rows"].tolist() == [0, 1, 2, 3]
+    assert a["masks"].dtype == np.float32 and all(np.array_equal(a["masks"][i], _fake_mask512(z).numpy()) for i, z in enumerate(r["last_zs"]))
+    assert all(a[n].dtype in (np.float32, np.float64) and np.array_equal(a[n], runs[1][n]) for n in names)
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--steps", "0"])
+    # 80 rows of 1 MiB each as float32: a sorted, seeded sample of 63 of them
+    out = tmp_path / "big"
+    r = bench.main(["--steps", "1", "--warmup", "0", "--batch", "80", "--micro", "80", "--slices", "96", "--no-extras", "--no-cpu-baseline",
+                    "--dump-outputs", str(out)], runtime=HostRuntime())
+    big = {n: np.load(out / f"{n}.npy") for n in names}
+    assert sum(os.path.getsize(out / f"{n}.npy") for n in names) <= 64 << 20
+    rows = big["rows"].astype(int)
+    assert len(rows) == 63 and list(rows) == sorted(set(rows)) and rows[-1] < 80
+    assert big["slice_z"].tolist() == [r["last_zs"][i] for i in rows]
+    assert all(np.array_equal(big["masks"][k], _fake_mask512(r["last_zs"][i]).numpy()) for k, i in enumerate(rows))
