@@ -159,6 +159,13 @@ int psam_bilinear_tokens(const float* in, long long in_bstride, int ld, int B, i
 int psam_prob_argmax(const float* logits, int B, int IH, int IW, int OH, int OW, float* prob, void* pred, int* fg_sum,
                      void* stream);
 int psam_broadcast_rows(const float* row, int D, float* out, int B, long long stride, long long off, void* stream);
+/* psam_prob_argmax twice, for P planes in one launch, keeping only what the connected components read: scores fp32 [P,2,IH,IW]
+ * -> [bilinear to OHxOW, align_corners=False] -> softmax -> argmax -> pred u8 [P,OH,OW], fg_sum int[P] (accumulated, caller
+ * zeroes; or NULL) -> softmax of the probabilities -> pfg2 fp32 [P,OH,OW] = its foreground channel (psam_ccl_batch's pfg,
+ * pfg_stride = OH*OW); prob fp32 [P,2,OH,OW] = the first softmax, or NULL. Replaces models/ProtoMedSAM.py:176-187 and
+ * util/utils.py:474-494 (the second softmax: util/utils.py:485). */
+int psam_prob2_argmax(const float* scores, int P, int IH, int IW, int OH, int OW, void* pred, float* pfg2, int* fg_sum,
+                      float* prob, void* stream);
 /* per-image min/max (order-preserving uint32 pairs).  models/ProtoSAM.py:660 */
 int psam_minmax(const float* x, int B, long long n_per_img, void* mm, void* stream);
 /* ((x-min)/(max-min)*255).astype(uint8) -> (u8 - mean)/std -> im2col(16x16) half; mean3/std3 are HOST pointers.
@@ -253,6 +260,12 @@ int psam_mask_upsample(const float* low, int planes, int IN, int MID, int varian
 /* pred = OR_b(upsample(low[b,sel]) > thr) sampled by F.interpolate(..., 'nearest') to OUT.  models/ProtoSAM.py:669-676 */
 int psam_mask_union(const float* low, int B, int C, int sel, int IN, int MID, int OUT, int variant, float thr,
                     float* pred, void* stream);
+/* psam_mask_union for many output masks in one launch, uint8: segs int32 [nseg,3] = (first prompt, prompt count, output index);
+ * out u8 [nout,OUT,OUT][segs[s,2]] = OR over low[first .. first+count-1, sel] of (upsample to MID > thr), nearest to OUT; a
+ * count of 0 writes zeros, a row pointing outside low [Pm,C,IN,IN] or out is skipped. variant 3 = sigmoid before the resize.
+ * Replaces models/ProtoMedSAM.py:49-60 (sigmoid -> bilinear -> > 0.5) and :219-220, per (slice, class). */
+int psam_mask_union_seg(const float* low, int Pm, int C, int sel, int IN, const int* segs, int nseg, int nout, int MID, int OUT,
+                        int variant, float thr, void* out, void* stream);
 
 /* Candidate statistics of SamAutomaticMaskGenerator without the full-resolution masks: for plane p (prompt p / nsel,
  * channel first + p % nsel of low [B,C,IN,IN]) over y < H, x < W of the MID x MID up-sampling, stats int32 [B*nsel, 8] =

@@ -45,6 +45,7 @@ SIGNATURES = {
     "psam_bilinear_tokens": [c_void_p, c_longlong, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p],
     "psam_prob_argmax": [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
     "psam_broadcast_rows": [c_void_p, c_int, c_void_p, c_int, c_longlong, c_longlong, c_void_p],
+    "psam_prob2_argmax": [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     "psam_minmax": [c_void_p, c_int, c_longlong, c_void_p, c_void_p],
     "psam_im2col3x3": [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p],
     "psam_cast_f16": [c_void_p, c_void_p, c_longlong, c_void_p],
@@ -65,6 +66,8 @@ SIGNATURES = {
     "psam_upscale_tail": [c_void_p] * 7 + [c_int, c_int, c_void_p],
     "psam_mask_upsample": [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p],
     "psam_mask_union": [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p],
+    "psam_mask_union_seg": [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float,
+                            c_void_p, c_void_p],
     "psam_mask_stats": [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_float,
                         c_void_p, c_void_p],
     "psam_im2col": [c_void_p] + [c_int] * 10 + [c_void_p, c_void_p],

@@ -6,6 +6,7 @@
 // TwoWayAttentionBlock :109-182, TwoWayTransformer :16-106), modeling/mask_decoder.py (predict_masks :112-149,
 // MLP :154-176) and the mask post-processing of modeling/sam.py (:133-161, :292-321) / models/ProtoSAM.py:669-676.
 #include "common.h"
+#include "interp.h"
 
 // =====================================================================================================
 // small_linear: y[g,m,n] = act(sum_k (x[g,m,k] [+ x2[g,m,k]]) W[g,n,k] + b[g,n]) (+ resid[g,m,n]);  fp32, few rows.
@@ -1094,52 +1095,7 @@ extern "C" int psam_upscale_tail(const float* u1, const float* lnw, const float*
 // Mask post-processing. variant 0: bilinear align_corners=False (pip segment_anything 1.0 `Sam`),
 // 1: bilinear align_corners=True (vendored `SamBatched`, sam.py:313-320), 2: nearest (vendored `Sam`, sam.py:154-160),
 // 3: sigmoid, then bilinear align_corners=False (MedSAM inference, models/ProtoMedSAM.py:49-60; threshold 0.5).
-struct Lin2 {
-  int i0, i1;
-  float l0, l1;
-};
-__device__ __forceinline__ Lin2 lin2(int dst, int in_size, int out_size, int align) {
-  float s;
-  if (align) {
-    const float sc = out_size > 1 ? (float)(in_size - 1) / (float)(out_size - 1) : 0.f;
-    s = sc * (float)dst;
-  } else {
-    const float sc = (float)in_size / (float)out_size;
-    s = sc * ((float)dst + 0.5f) - 0.5f;
-    s = s < 0.f ? 0.f : s;
-  }
-  int i0 = (int)s;
-  if (i0 > in_size - 1) i0 = in_size - 1;
-  Lin2 r;
-  r.i0 = i0;
-  r.i1 = i0 + (i0 < in_size - 1 ? 1 : 0);
-  float l1 = s - (float)i0;
-  l1 = l1 < 0.f ? 0.f : (l1 > 1.f ? 1.f : l1);
-  r.l1 = l1;
-  r.l0 = 1.f - l1;
-  return r;
-}
-__device__ __forceinline__ float up_sample(const float* __restrict__ p, int IN, int MID, int y, int x, int variant) {
-  // value of interpolate(p[IN,IN] -> [MID,MID]) at (y, x)
-  if (variant == 2) {
-    const float sc = (float)IN / (float)MID;
-    int sy = (int)floorf((float)y * sc), sx = (int)floorf((float)x * sc);
-    sy = sy < IN - 1 ? sy : IN - 1;
-    sx = sx < IN - 1 ? sx : IN - 1;
-    return p[(size_t)sy * IN + sx];
-  }
-  Lin2 ly = lin2(y, IN, MID, variant == 1), lx = lin2(x, IN, MID, variant == 1);
-  const float* r0 = p + (size_t)ly.i0 * IN;
-  const float* r1 = p + (size_t)ly.i1 * IN;
-  float a = r0[lx.i0], b = r0[lx.i1], c = r1[lx.i0], d = r1[lx.i1];
-  if (variant == 3) {  // torch.sigmoid(low_res_logits) BEFORE the bilinear resize (models/ProtoMedSAM.py:49-56)
-    a = 1.f / (1.f + expf(-a));
-    b = 1.f / (1.f + expf(-b));
-    c = 1.f / (1.f + expf(-c));
-    d = 1.f / (1.f + expf(-d));
-  }
-  return ly.l0 * (lx.l0 * a + lx.l1 * b) + ly.l1 * (lx.l0 * c + lx.l1 * d);
-}
+// (Lin2 / lin2 / up_sample live in interp.h.)
 
 // masks [B, C, IN, IN] logits -> logits at [B, C, MID, MID] (the predictor's `masks` before thresholding when the image
 // handed to SAM is MID x MID, so the second interpolate of postprocess_masks is the identity)

@@ -15,30 +15,7 @@
 //   src = max(scale*(dst+0.5)-0.5, 0), scale = in/out in fp32; i0 = (int)src, i1 = i0 + (i0 < in-1),
 //   l1 = src - i0, l0 = 1 - l1;  out = h0*(w0*p00 + w1*p01) + h1*(w0*p10 + w1*p11).
 #include "common.h"
-
-struct Lin {
-  int i0, i1;
-  float l0, l1;
-};
-__device__ __forceinline__ Lin lin_src(int dst, float scale, int in_size) {
-  float s = scale * ((float)dst + 0.5f) - 0.5f;
-  s = s < 0.f ? 0.f : s;
-  int i0 = (int)s;
-  if (i0 > in_size - 1) i0 = in_size - 1;
-  Lin r;
-  r.i0 = i0;
-  r.i1 = i0 + (i0 < in_size - 1 ? 1 : 0);
-  float l1 = s - (float)i0;
-  l1 = l1 < 0.f ? 0.f : (l1 > 1.f ? 1.f : l1);
-  r.l1 = l1;
-  r.l0 = 1.f - l1;
-  return r;
-}
-__device__ __forceinline__ float bilerp(const float* __restrict__ p, int W, const Lin& y, const Lin& x) {
-  const float* r0 = p + (size_t)y.i0 * W;
-  const float* r1 = p + (size_t)y.i1 * W;
-  return y.l0 * (x.l0 * r0[x.i0] + x.l1 * r0[x.i1]) + y.l1 * (x.l0 * r1[x.i0] + x.l1 * r1[x.i1]);
-}
+#include "interp.h"
 
 // out[(b*np + py*npw + px)*Kpad + c*P*P + ky*P + kx] = resize(img)[b,c,py*P+ky,px*P+kx]; zero for k >= 3*P*P
 __global__ void patchify_bilinear_kernel(const float* __restrict__ img, int B, int C, int H, int W, int S, int P,

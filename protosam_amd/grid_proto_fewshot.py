@@ -268,9 +268,41 @@ class FewShotSeg(nn.Module):
         tokens are matched against every class's bank. fore_masks: list of [1,H,W] masks. Returns a list of logits [1,2,H,W],
         each identical to `forward(...)` of that class alone."""
         S, g = self._grid()
-        C = self.encoder.embed_dim
         img_size = supp_img.shape[-2:]
         pool_w = val_wsize if (isval and val_wsize is not None) else self.cls_unit.kernel_size[0]
+        banks = self._class_banks(supp_img, fore_masks, pool_w)
+        qry_tok, q_bstride, q_ld = self._patch_tokens(qry_img)
+        B = qry_tok.shape[0]
+        outs = []
+        for bank in banks:
+            pred = self.cls_unit.scores_token_major(qry_tok, q_bstride, q_ld, B, g * g, bank)
+            self._check_bank(bank)
+            outs.append(ops.bilinear_nchw(pred.view(B, 2, g, g), img_size[0], img_size[1]))
+        return outs
+
+    @torch.no_grad()
+    def class_scores(self, supp_img, fore_masks, qry_imgs, isval=True, val_wsize=None):
+        """`forward_classes` for B query slices without the per-class resize to the image size: ONE encoder forward of the B queries
+        matched against every class's bank, each class's scores written straight into one tensor. Returns fp32 [C, B, 2, g, g]
+        (class-major: plane c * B + b of a [C*B, 2, g, g] view is class c of slice b); the bilinear resize of plane (c, b) to the
+        image size is `forward_classes(supp_img, fore_masks, qry_imgs[b:b+1])[c]`. Uses the same support-bank cache."""
+        S, g = self._grid()
+        pool_w = val_wsize if (isval and val_wsize is not None) else self.cls_unit.kernel_size[0]
+        banks = self._class_banks(supp_img, fore_masks, pool_w)
+        qry_tok, q_bstride, q_ld = self._patch_tokens(qry_imgs)
+        B = qry_tok.shape[0]
+        out = torch.empty((len(banks), B, 2, g, g), dtype=torch.float32, device=qry_imgs.device)
+        for c, bank in enumerate(banks):
+            self.cls_unit.scores_token_major(qry_tok, q_bstride, q_ld, B, g * g, bank, pred=out[c].view(B, 2, g * g))
+            self._check_bank(bank)
+        return out
+
+    def _class_banks(self, supp_img, fore_masks, pool_w):
+        """One prototype bank per class mask of one support image (`forward_classes`, `class_scores`), cached while the support
+        image and masks are the same objects, unmodified. Encodes the support through the encoder's token workspace: call it
+        BEFORE the query is encoded."""
+        S, g = self._grid()
+        C = self.encoder.embed_dim
         key = (supp_img, supp_img._version, tuple((m, m._version) for m in fore_masks), pool_w, getattr(self.encoder, "_weights_epoch", 0))
         hit = getattr(self, "_cls_cache", None)
         if (self.cache_support and hit is not None and hit[0][0] is supp_img and hit[0][1] == key[1] and hit[0][3:] == key[3:]
@@ -284,14 +316,7 @@ class FewShotSeg(nn.Module):
                 fg2 = fg.reshape(fg.shape[-2], fg.shape[-1]).float().contiguous()
                 banks.append(self.cls_unit.build_bank(tok, C, g, g, fg2, pool_w, FG_THRESH, force_mode=-1, bank=None, bg_mask=None))
             self._cls_cache = (key, banks)
-        qry_tok, q_bstride, q_ld = self._patch_tokens(qry_img)
-        B = qry_tok.shape[0]
-        outs = []
-        for bank in banks:
-            pred = self.cls_unit.scores_token_major(qry_tok, q_bstride, q_ld, B, g * g, bank)
-            self._check_bank(bank)
-            outs.append(ops.bilinear_nchw(pred.view(B, 2, g, g), img_size[0], img_size[1]))
-        return outs
+        return banks
 
     def _check_bank(self, bank):
         """The reference raises inside F.conv2d when a bank is empty (alpmodule.py:193-196). One 8-int D2H read."""

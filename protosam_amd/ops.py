@@ -605,6 +605,31 @@ def prob_argmax(logits, OH, OW, prob=None, pred=None, fg_sum=None):
     return prob, pred
 
 
+def prob2_argmax(scores, OH, OW, pred=None, pfg2=None, fg_sum=None, prob=None):
+    """scores fp32 [P,2,IH,IW] -> (pred uint8 [P,OH,OW], pfg2 fp32 [P,OH,OW]) in one launch (psam_prob2_argmax): bilinear to
+    (OH,OW) unless equal, softmax, argmax, then the foreground channel of a second softmax - the same bits as `prob_argmax` applied
+    twice (ProtoMedSAM.py:176-187, util/utils.py:485). fg_sum int32 [P] is accumulated (zero it first); prob (optional, fp32
+    [P,2,OH,OW]) receives the first softmax."""
+    _req(scores, torch.float32, "scores")
+    assert scores.is_contiguous() and scores.dim() == 4 and scores.shape[1] == 2
+    P, dev = scores.shape[0], scores.device
+    if pred is None:
+        pred = torch.empty((P, OH, OW), dtype=torch.uint8, device=dev)
+    if pfg2 is None:
+        pfg2 = torch.empty((P, OH, OW), dtype=torch.float32, device=dev)
+    _req(pfg2, torch.float32, "pfg2"); _req(prob, torch.float32, "prob")
+    assert pred.dtype == torch.uint8 and pred.is_contiguous() and pred.numel() >= P * OH * OW
+    assert pfg2.is_contiguous() and pfg2.numel() >= P * OH * OW
+    assert prob is None or (prob.is_contiguous() and prob.numel() >= P * 2 * OH * OW)
+    assert fg_sum is None or (fg_sum.dtype == torch.int32 and fg_sum.is_contiguous() and fg_sum.numel() >= P)
+    h = _tstart("prob2_argmax")
+    st = _lib.lib().psam_prob2_argmax(_ptr(scores), P, scores.shape[2], scores.shape[3], OH, OW, _ptr(pred), _ptr(pfg2),
+                                      _ptr(fg_sum), _ptr(prob), _stream())
+    _tstop(h, P * (2 * scores.shape[2] * scores.shape[3] * 4 + OH * OW * (5 + (8 if prob is not None else 0))))
+    _lib.check(st, "psam_prob2_argmax")
+    return pred, pfg2
+
+
 def broadcast_rows(row, out, B, stride, off):
     _req(row, torch.float32, "row"); _req(out, torch.float32, "out")
     st = _lib.lib().psam_broadcast_rows(_ptr(row), row.numel(), _ptr(out), B, stride, off, _stream())
@@ -917,6 +942,32 @@ def mask_union(low, sel, MID, OUT, variant, thr=0.0, pred=None):
     return pred
 
 
+def mask_union_seg(low, sel, segs, nout, MID, OUT, variant, thr, out=None):
+    """Every output mask of a batch in one launch (psam_mask_union_seg): low fp32 [Pm,C,IN,IN] (None when Pm = 0), segs int32
+    [nseg,3] device tensor of (first prompt, prompt count, output index) -> out uint8 [nout,OUT,OUT], out[o] = what
+    `mask_union(low[first:first+count], sel, MID, OUT, variant, thr).to(torch.uint8)` gives (zeros for a count of 0). Outputs no
+    segment names are left as they are."""
+    assert segs.dtype == torch.int32 and segs.is_cuda and segs.is_contiguous() and segs.dim() == 2 and segs.shape[1] == 3
+    if low is not None:
+        _req(low, torch.float32, "low")
+        assert low.is_contiguous() and low.dim() == 4
+        Pm, C, IN, _ = low.shape
+    else:
+        Pm, C, IN = 0, sel + 1, 1
+    if out is None:
+        out = torch.empty((nout, OUT, OUT), dtype=torch.uint8, device=segs.device)
+    assert out.dtype == torch.uint8 and out.is_contiguous() and out.numel() >= nout * OUT * OUT
+    nseg = segs.shape[0]
+    if nseg == 0:
+        return out
+    h = _tstart("mask_union_seg")
+    st = _lib.lib().psam_mask_union_seg(_ptr(low), Pm, C, sel, IN, _ptr(segs), nseg, nout, MID, OUT, variant, float(thr), _ptr(out),
+                                        _stream())
+    _tstop(h, nseg * OUT * OUT)
+    _lib.check(st, "psam_mask_union_seg")
+    return out
+
+
 def mask_downscale(masks, wts, g, eps=1e-6, out=None):
     """PromptEncoder.mask_downscaling: masks fp32 [n,4g,4g] -> dense embeddings fp32 [n, g*g, 256] (token-major)."""
     _req(masks, torch.float32, "masks"); _req(wts, torch.float32, "wts")
@@ -1094,6 +1145,22 @@ def ccl_batch(pred_u8, prob, ws, fg_sum=None):
     assert prob.is_contiguous() and prob.shape[1] == 2
     h = _tstart("ccl")
     st = _lib.lib().psam_ccl_batch(_ptr(pred_u8), _ptr(prob[0, 1]), 2 * ws.H * ws.W, B, ws.H, ws.W, ws.cap, _ptr(ws.labels_b),
+                                  _ptr(ws.parent_b), _ptr(ws.counters_b), _ptr(ws.roots_b), _ptr(ws.acc_i_b), _ptr(ws.acc_u_b),
+                                  _ptr(ws.acc_d_b), _ptr(fg_sum), _ptr(ws.tabs), _stream())
+    _tstop(h, B * ws.H * ws.W * (1 + 4 + 4))
+    _lib.check(st, "psam_ccl_batch")
+    return ws
+
+
+def ccl_planes(pred_u8, pfg, ws, fg_sum=None):
+    """`ccl_batch` on planes whose foreground probability is a plane of its own: pred uint8 [B,H,W], pfg fp32 [B,H,W] (e.g.
+    prob2_argmax's pfg2) -> ws.labels_b[b], ws.tabs[b]."""
+    B = pred_u8.shape[0]
+    assert pred_u8.dtype == torch.uint8 and pred_u8.is_cuda and pred_u8.is_contiguous() and B <= ws.slots
+    _req(pfg, torch.float32, "pfg")
+    assert pfg.is_contiguous() and pfg.shape[0] == B and pfg[0].numel() == ws.H * ws.W
+    h = _tstart("ccl")
+    st = _lib.lib().psam_ccl_batch(_ptr(pred_u8), _ptr(pfg), ws.H * ws.W, B, ws.H, ws.W, ws.cap, _ptr(ws.labels_b),
                                   _ptr(ws.parent_b), _ptr(ws.counters_b), _ptr(ws.roots_b), _ptr(ws.acc_i_b), _ptr(ws.acc_u_b),
                                   _ptr(ws.acc_d_b), _ptr(fg_sum), _ptr(ws.tabs), _stream())
     _tstop(h, B * ws.H * ws.W * (1 + 4 + 4))

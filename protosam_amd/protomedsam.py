@@ -14,11 +14,17 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .protosam import MAX_COMPONENTS, MAX_COMPONENTS_LARGE, ModelWrapper
+from .protosam import DECODER_CHUNK, MAX_COMPONENTS, MAX_COMPONENTS_LARGE, ModelWrapper, ProtoSAM
 from .segment_anything import sam_model_registry
+
+CCL_SLOTS = 32   # planes per connected-components launch chain of the batched paths (~8 MB of CCL scratch per slot at 1024^2)
 
 
 class ProtoMedSAM(nn.Module):
+    # the coarse-only paths are ProtoSAM's (ProtoMedSAM.py:163-172 is ProtoSAM.py:580-590)
+    _coarse_only = ProtoSAM._coarse_only
+    _coarse_only_batch = ProtoSAM._coarse_only_batch
+
     def __init__(self, image_size, coarse_segmentation_model: ModelWrapper,
                  sam_pretrained_path="pretrained_model/medsam_vit_b.pth", debug=False, use_cca=False,
                  coarse_pred_only=False):
@@ -271,5 +277,231 @@ class ProtoMedSAM(nn.Module):
             for k, c in enumerate(owners):
                 seg = ops.mask_union(masks[k:k + 1], 0, S, original_size, 3, 0.5)
                 results[c] = (seg.to(torch.uint8).clone(), [iou_h[k:k + 1]])
+            self.last_stats.update(low_res=masks, iou=iou)
+        return results
+
+    # ---- batched paths: B slices (x C classes) per call --------------------------------------------------------------------
+    def _batch_bufs(self, dev, P, B):
+        """Buffers of the batched paths, grown to the largest P (planes) / B (slices) seen: per plane the uint8 arg-max map, the
+        softmax(softmax) foreground plane, the foreground count and (pinned) the component table; per slice the encoder input."""
+        S = self.medsam.image_encoder.img_size
+        bb = self.__dict__.setdefault("_bbufs", {})
+        if bb.get("P", 0) < P:
+            bb.update(P=P, pred=None, pfg2=None)          # (drop the old planes before allocating the larger ones)
+            bb.update(pred=torch.empty((P, S, S), dtype=torch.uint8, device=dev),
+                      pfg2=torch.empty((P, S, S), dtype=torch.float32, device=dev),
+                      fg=torch.zeros(P, dtype=torch.int32, device=dev), fg_host=torch.zeros(P, dtype=torch.int32).pin_memory(),
+                      tabs_host=torch.empty((P, ops.CC_HDR + ops.CC_STRIDE * MAX_COMPONENTS), dtype=torch.float64).pin_memory(),
+                      fg_event=torch.cuda.Event(), event=torch.cuda.Event())
+        if bb.get("B", 0) < B:
+            bb.update(B=B, q1024=None)
+            bb.update(q1024=torch.empty((B, 3, S, S), dtype=torch.float32, device=dev),
+                      mm=torch.empty(2 * B, dtype=torch.int32, device=dev),
+                      patches=torch.empty((B * 4096, 768), dtype=torch.float16, device=dev))
+        slots = min(P, CCL_SLOTS)
+        if getattr(self, "_ccl_chunk", None) is None or self._ccl_chunk.slots < slots:
+            self._ccl_chunk = None
+            self._ccl_chunk = ops.CclWorkspace(S, S, MAX_COMPONENTS, dev, slots=slots)
+        return bb
+
+    def _coarse_to_components(self, scores, P, bb):
+        """scores fp32 [P,2,h,w] -> one psam_prob2_argmax launch (bilinear to 1024 unless already there, softmax, arg-max, foreground
+        count, softmax again: ProtoMedSAM.py:176-187, util/utils.py:485) -> connected components in chunks of CCL_SLOTS planes, every
+        table on its way to pinned host memory. Nothing waits: bb["fg_event"] marks the foreground counts, bb["event"] the tables."""
+        S = self.medsam.image_encoder.img_size
+        pred, pfg2, fg = bb["pred"][:P], bb["pfg2"][:P], bb["fg"][:P]
+        fg.zero_()
+        ops.prob2_argmax(scores, S, S, pred=pred, pfg2=pfg2, fg_sum=fg)
+        bb["fg_host"][:P].copy_(fg, non_blocking=True)
+        bb["fg_event"].record()
+        cw = self._ccl_chunk
+        for c0 in range(0, P, cw.slots):
+            c1 = min(c0 + cw.slots, P)
+            ops.ccl_planes(pred[c0:c1], pfg2[c0:c1], cw, fg_sum=fg[c0:c1])
+            bb["tabs_host"][c0:c1].copy_(cw.tabs[:c1 - c0], non_blocking=True)   # (stream order: copied before the next chunk)
+        bb["event"].record()
+
+    def _plane_table(self, p, bb, what):
+        """Component table of plane p (host numpy); a plane with more components than the fast table is labelled again with the large
+        table, as `forward` does (synchronous, rare)."""
+        tab = bb["tabs_host"][p].numpy()
+        if int(tab[0]) > int(tab[1]):
+            if getattr(self, "_ccl_big", None) is None:
+                self._ccl_big = ops.CclWorkspace(1024, 1024, MAX_COMPONENTS_LARGE, bb["pred"].device)
+            tab = ops.ccl(bb["pred"][p], bb["pfg2"][p], self._ccl_big, fg_sum=bb["fg"][p:p + 1]).tab.cpu().numpy()
+            if int(tab[0]) > int(tab[1]):
+                raise RuntimeError(f"{what}: {int(tab[0])} connected components exceed the table capacity {MAX_COMPONENTS_LARGE}")
+        return tab
+
+    def _medsam_features(self, imgs, bb):
+        """min-max to [0,1] -> im2col -> MedSAM image encoder for the slices `imgs` [B',3,H,W] (ProtoMedSAM.py:203-205)
+        -> token-major embeddings [B', 4096, 256]."""
+        sam = self.medsam
+        S = sam.image_encoder.img_size
+        n = imgs.shape[0]
+        q = imgs.float().contiguous()
+        if tuple(q.shape[-2:]) != (S, S):
+            q = ops.bilinear_nchw(q, S, S, out=bb["q1024"][:n])
+        mm, patches = bb["mm"][:2 * n], bb["patches"][:n * 4096]
+        ops.minmax(q, n, mm=mm)
+        ops.sam_patchify(q, mm, S, sam.image_encoder.patch_size, (0.0, 0.0, 0.0), (1.0, 1.0, 1.0), False, out=patches)
+        return sam.image_encoder.encode_patches(patches, n)
+
+    def _decode_boxes(self, feat_tok, boxes, img_idx):
+        """One box prompt per row of `boxes` (XYXY in the 1024 frame) on image img_idx[i] of feat_tok, all through the decoder in
+        chunks of DECODER_CHUNK prompt sets (multimask_output=False: mask 0). -> low-res masks [n,4,256,256], iou [n,4]."""
+        sam = self.medsam
+        S = sam.image_encoder.img_size
+        dev = feat_tok.device
+        n = len(boxes)
+        coords = torch.from_numpy(np.stack(boxes).reshape(-1, 2, 2).astype(np.float32)).to(dev)
+        labels = torch.from_numpy(np.tile(np.array([[2, 3]], dtype=np.int32), (n, 1))).to(dev)
+        iop = torch.tensor(img_idx, dtype=torch.int32).to(dev)
+        pe = sam.prompt_encoder._packed()
+        dpk = sam.mask_decoder._packed()
+        tokens = ops.prompt_tokens(coords, labels, pe["G"], pe["type_emb"], dpk["out_tok"], n, 2, float(S))
+        masks = torch.empty((n, 4, 256, 256), dtype=torch.float32, device=dev)
+        iou = torch.empty((n, 4), dtype=torch.float32, device=dev)
+        for c0 in range(0, n, DECODER_CHUNK):
+            c1 = min(c0 + DECODER_CHUNK, n)
+            sam.mask_decoder.predict_masks_tokens(feat_tok, pe["pe_tok"], tokens[c0:c1].contiguous(), pe["no_mask"],
+                                                  img_of_prompt=iop[c0:c1].contiguous(), masks_out=masks[c0:c1],
+                                                  iou_out=iou[c0:c1])
+        return masks, iou
+
+    @torch.no_grad()
+    def forward_batch(self, query_images, coarse_model_input, degrees_rotate=0):
+        """MI355X extension, `ProtoSAM.forward_batch`'s contract: B query slices [B,3,H,W] through every stage as one batch.
+        `coarse_model_input`: one input (shared support set) or a list of (input, n) pairs in batch order. Returns a list of
+        (mask, [conf]) per slice, each what `forward` gives for that slice (uint8 [H,W]; int64 zeros and [0] for an empty coarse
+        mask). Pipeline: one psam_prob2_argmax over the B planes, one connected-components chain (per CCL_SLOTS planes), the
+        MedSAM encoder on the slices with a component only (as one sub-batch), one box-prompted decoder call, one
+        psam_mask_union_seg."""
+        B = query_images.shape[0]
+        original_size = query_images.shape[-2]
+        dev = query_images.device
+        logits = ProtoSAM._coarse_logits(self, query_images, coarse_model_input, degrees_rotate)    # [B,2,H,W]
+        if self.coarse_pred_only:                                                                   # ProtoMedSAM.py:163-172
+            return self._coarse_only_batch(logits, original_size)
+        S = self.medsam.image_encoder.img_size
+        bb = self._batch_bufs(dev, B, B)
+        self._coarse_to_components(logits.float().contiguous(), B, bb)
+        # the encoder runs on the slices with foreground only (ProtoMedSAM.py:194-197 returns before it); it is enqueued before the
+        # host waits for the tables, so that wait overlaps it
+        bb["fg_event"].synchronize()
+        keep = [b for b in range(B) if int(bb["fg_host"][b]) > 0]
+        feat_row = [-1] * B
+        feat_tok = None
+        if keep:
+            sub = query_images if len(keep) == B else query_images[torch.tensor(keep, device=dev)]
+            feat_tok = self._medsam_features(sub, bb)
+            for i, b in enumerate(keep):
+                feat_row[b] = i
+        bb["event"].synchronize()
+        results = [None] * B
+        stats, boxes, img_idx, owners = [], [], [], []
+        for b in range(B):
+            tab = self._plane_table(b, bb, f"slice {b}")
+            n = int(tab[1])
+            stats.append(dict(n_components=int(tab[0]), n_prompts=0, prompt=None))
+            if n == 0:                                                                              # :194-197
+                results[b] = (torch.zeros((original_size, original_size), dtype=torch.int64, device=dev), [0])
+                continue
+            rows = tab[ops.CC_HDR:ops.CC_HDR + ops.CC_STRIDE * n].reshape(n, ops.CC_STRIDE)
+            if self.use_cca:
+                rows = rows[int(tab[3]):int(tab[3]) + 1]
+            if rows.shape[0] != 1:
+                raise NotImplementedError(f"slice {b} of the batch: ProtoMedSAM with several components is undefined in the "
+                                          "reference (SURVEY Q16); use use_cca=True")
+            stats[b].update(n_prompts=1, prompt=len(boxes))
+            boxes.append(rows[0, 3:7] / np.array([S, S, S, S]) * max(self.image_size))              # :201-202
+            img_idx.append(feat_row[b])
+            owners.append(b)
+        self.last_stats = stats[0] if B == 1 else dict(per_slice=stats)
+        if owners:
+            masks, iou = self._decode_boxes(feat_tok, boxes, img_idx)
+            segs = torch.tensor([[k, 1, k] for k in range(len(owners))], dtype=torch.int32).to(dev)
+            out = ops.mask_union_seg(masks, 0, segs, len(owners), S, original_size, 3, 0.5)       # sigmoid -> bilinear -> > 0.5
+            iou_h = iou[:, 0:1].cpu().numpy()
+            for k, b in enumerate(owners):
+                results[b] = (out[k], [iou_h[k:k + 1]])
+            self.last_stats.update(low_res=masks, iou=iou)
+        return results
+
+    @torch.no_grad()
+    def forward_classes_batch(self, query_images, support_image, support_masks, val_wsize=2, out=None):
+        """The config-5 throughput path: B query slices [B,3,H,W] x C classes (support_masks: C masks of `support_image`) in one
+        call. Returns results[b][c] = (mask, [conf]), equal to `forward_classes(query_images[b:b+1], ...)[c]`: the masks of the
+        classes with a component are views of one uint8 [B,C,H,W] tensor (`out` if given), the others int64 zeros and [0] (that
+        tensor holds zeros there too). Only `use_cca=True`, as `forward_classes`.
+        Pipeline: ONE DINOv2 forward of the B slices matched against the C banks (FewShotSeg.class_scores: scores at grid
+        resolution, class-major planes c*B + b), ONE psam_prob2_argmax over the P = B*C planes, the connected components in chunks
+        of CCL_SLOTS planes, ONE MedSAM encoder forward of the slices where some class has a component, ONE decoder call over every
+        (slice, class) box (chunked by DECODER_CHUNK), ONE psam_mask_union_seg into [B,C,H,W].
+        Extra device memory at B = 32, C = 4, 1024^2: 640 MiB of per-plane maps (uint8 arg-max + fp32 softmax(softmax)), ~260 MiB of
+        CCL scratch (32 slots), 128 MiB of output masks, 128 MiB of low-res decoder masks, plus the encoder's 32-slice workspace
+        and the decoder's per-prompt workspace (measured peak: see DESIGN.md section 6)."""
+        if not self.use_cca or self.coarse_pred_only:
+            raise NotImplementedError("forward_classes_batch: use_cca=True, coarse_pred_only=False")
+        B, H = query_images.shape[0], query_images.shape[-2]
+        dev = query_images.device
+        alp = self.coarse_segmentation_model.model
+        sc = alp.class_scores(support_image, support_masks, query_images, isval=True, val_wsize=val_wsize)   # [C,B,2,g,g]
+        C, g = sc.shape[0], sc.shape[-1]
+        P = C * B
+        S = self.medsam.image_encoder.img_size
+        sc = sc.view(P, 2, g, g)
+        img_size = tuple(support_image.shape[-2:])
+        if img_size != (S, S):     # forward_classes resizes to the image size first, then to 1024 (two resamplings)
+            sc = ops.bilinear_nchw(sc, img_size[0], img_size[1])
+        bb = self._batch_bufs(dev, P, B)
+        self._coarse_to_components(sc, P, bb)
+        bb["fg_event"].synchronize()
+        fgh = bb["fg_host"][:P].view(C, B)
+        keep = [b for b in range(B) if int(fgh[:, b].max()) > 0]
+        feat_row = [-1] * B
+        feat_tok = None
+        if keep:
+            sub = query_images if len(keep) == B else query_images[torch.tensor(keep, device=dev)]
+            feat_tok = self._medsam_features(sub, bb)
+            for i, b in enumerate(keep):
+                feat_row[b] = i
+        bb["event"].synchronize()
+        results = [[None] * C for _ in range(B)]
+        boxes, img_idx, owners = [], [], []
+        for b in range(B):
+            for c in range(C):
+                p = c * B + b
+                tab = bb["tabs_host"][p].numpy()
+                if int(tab[0]) > int(tab[1]):
+                    raise RuntimeError(f"slice {b}, class {c}: {int(tab[0])} connected components exceed the fast table; use "
+                                       "forward() for this slice")
+                n = int(tab[1])
+                if n == 0:
+                    results[b][c] = (torch.zeros((H, H), dtype=torch.int64, device=dev), [0])
+                    continue
+                row = tab[ops.CC_HDR + ops.CC_STRIDE * int(tab[3]):ops.CC_HDR + ops.CC_STRIDE * (int(tab[3]) + 1)]
+                boxes.append(row[3:7] / np.array([S, S, S, S]) * max(self.image_size))
+                img_idx.append(feat_row[b])
+                owners.append((b, c))
+        if out is None:
+            out = torch.empty((B, C, H, H), dtype=torch.uint8, device=dev)
+        assert out.shape == (B, C, H, H) and out.dtype == torch.uint8 and out.is_contiguous()
+        prompt = {bc: k for k, bc in enumerate(owners)}
+        # one segment per (slice, class): its prompt, or none (zeros)
+        segs = np.zeros((B * C, 3), dtype=np.int32)
+        for b in range(B):
+            for c in range(C):
+                k = prompt.get((b, c))
+                segs[b * C + c] = (k, 1, b * C + c) if k is not None else (0, 0, b * C + c)
+        masks = iou = None
+        if owners:
+            masks, iou = self._decode_boxes(feat_tok, boxes, img_idx)
+        ops.mask_union_seg(masks, 0, torch.from_numpy(segs).to(dev), B * C, S, H, 3, 0.5, out=out.view(B * C, H, H))
+        self.last_stats = dict(n_slices=B, n_classes=C, n_prompted=len(owners), prompt=prompt, n_encoded=len(keep))
+        if owners:
+            iou_h = iou[:, 0:1].cpu().numpy()
+            for k, (b, c) in enumerate(owners):
+                results[b][c] = (out[b, c], [iou_h[k:k + 1]])
             self.last_stats.update(low_res=masks, iou=iou)
         return results

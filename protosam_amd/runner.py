@@ -104,6 +104,38 @@ def run_slices(model, vol, sup_imgs, sup_masks, zs, device, out=None, batch=1, m
     return out, stats
 
 
+@torch.no_grad()
+def run_slices_classes(model, vol, sup_imgs, sup_masks_per_part, zs, device, batch=16, out=None):
+    """The multi-class form of `run_slices` (BASELINE config 5; the reference runs one 1-way episode per class, validation.py:207):
+    slices `zs` of `vol` [n,S,S] against C classes, `batch` slices per `model.forward_classes_batch` call (a ProtoMedSAM). Part p
+    of the scan has its own support image sup_imgs[p] and C masks sup_masks_per_part[p]; batches are cut at part boundaries.
+    Returns uint8 masks [len(zs), C, S, S] (the batch's output tensor is a slice of it) and the number of prompted classes per
+    slice."""
+    n, S = vol.shape[0], vol.shape[-1]
+    C = len(sup_masks_per_part[0])
+    if out is None:
+        out = torch.zeros((len(zs), C, S, S), dtype=torch.uint8, device=device)
+    stats = [0] * len(zs)
+    i = 0
+    while i < len(zs):
+        part = part_assign(zs[i], n)
+        j = i
+        while j < len(zs) and j - i < batch and part_assign(zs[j], n) == part:
+            j += 1
+        idx = torch.tensor(zs[i:j], device=device)
+        q = vol[idx][:, None].expand(j - i, 3, S, S).contiguous()
+        dst = out[i:j]
+        res = model.forward_classes_batch(q, sup_imgs[part], sup_masks_per_part[part], out=dst)
+        for k, per_class in enumerate(res):
+            for c, (mask, _) in enumerate(per_class):
+                if mask.data_ptr() != dst[k, c].data_ptr():        # (an empty class: int64 zeros, and zeros in `dst` already)
+                    dst[k, c].copy_(mask)
+        for (k, _) in model.last_stats.get("prompt", {}):          # (slice, class) pairs that went to the decoder
+            stats[i + k] += 1
+        i = j
+    return out, stats
+
+
 def gather_masks(local, world):
     """One all-gather of the per-rank uint8 masks (RCCL on GPUs, gloo on CPU). [k,S,S] -> [world*k,S,S] (rank-major)."""
     if world == 1 or not dist.is_initialized():
