@@ -262,30 +262,12 @@ class FewShotSeg(nn.Module):
         return out
 
     @torch.no_grad()
-    def forward_classes(self, supp_img, fore_masks, qry_img, isval=True, val_wsize=None):
-        """Several 1-way episodes on the SAME support / query image pair (the multi-class loop of /root/reference/validation.py:207,
-        BASELINE config 5: one prototype bank per class): the support and the query image are each encoded ONCE and the query
-        tokens are matched against every class's bank. fore_masks: list of [1,H,W] masks. Returns a list of logits [1,2,H,W],
-        each identical to `forward(...)` of that class alone."""
-        S, g = self._grid()
-        img_size = supp_img.shape[-2:]
-        pool_w = val_wsize if (isval and val_wsize is not None) else self.cls_unit.kernel_size[0]
-        banks = self._class_banks(supp_img, fore_masks, pool_w)
-        qry_tok, q_bstride, q_ld = self._patch_tokens(qry_img)
-        B = qry_tok.shape[0]
-        outs = []
-        for bank in banks:
-            pred = self.cls_unit.scores_token_major(qry_tok, q_bstride, q_ld, B, g * g, bank)
-            self._check_bank(bank)
-            outs.append(ops.bilinear_nchw(pred.view(B, 2, g, g), img_size[0], img_size[1]))
-        return outs
-
-    @torch.no_grad()
     def class_scores(self, supp_img, fore_masks, qry_imgs, isval=True, val_wsize=None):
-        """`forward_classes` for B query slices without the per-class resize to the image size: ONE encoder forward of the B queries
-        matched against every class's bank, each class's scores written straight into one tensor. Returns fp32 [C, B, 2, g, g]
-        (class-major: plane c * B + b of a [C*B, 2, g, g] view is class c of slice b); the bilinear resize of plane (c, b) to the
-        image size is `forward_classes(supp_img, fore_masks, qry_imgs[b:b+1])[c]`. Uses the same support-bank cache."""
+        """Several 1-way episodes on the SAME support image (the multi-class loop of /root/reference/validation.py:207, BASELINE
+        config 5: one prototype bank per class mask in fore_masks, each [1,H,W]) for B query slices: the support is encoded ONCE,
+        the B queries in ONE encoder forward, and their tokens are matched against every class's bank, each class's scores written
+        straight into one tensor. Returns fp32 [C, B, 2, g, g] (class-major: plane c * B + b of a [C*B, 2, g, g] view is class c of
+        slice b); at B = 1 the bilinear resize of plane c to the image size is the logits `forward(...)` of class c alone."""
         S, g = self._grid()
         pool_w = val_wsize if (isval and val_wsize is not None) else self.cls_unit.kernel_size[0]
         banks = self._class_banks(supp_img, fore_masks, pool_w)
@@ -298,7 +280,7 @@ class FewShotSeg(nn.Module):
         return out
 
     def _class_banks(self, supp_img, fore_masks, pool_w):
-        """One prototype bank per class mask of one support image (`forward_classes`, `class_scores`), cached while the support
+        """One prototype bank per class mask of one support image (`class_scores`), cached while the support
         image and masks are the same objects, unmodified. Encodes the support through the encoder's token workspace: call it
         BEFORE the query is encoded."""
         S, g = self._grid()

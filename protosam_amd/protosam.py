@@ -517,21 +517,20 @@ class ProtoSAM(nn.Module):
             self._ccl = ops.CclWorkspace(1024, 1024, MAX_COMPONENTS, dev, slots=max(B, 1))
         return self._bufs[key]
 
-    def _ccl_overflow(self, b, bufs, output_p, pred, S):
-        """Slice `b` has more than MAX_COMPONENTS connected components: label it again with a MAX_COMPONENTS_LARGE table
-        (synchronous, rare) and refresh the per-slice side products that were derived from the truncated labelling."""
-        dev = pred.device
-        if getattr(self, "_ccl_big", None) is None:
-            self._ccl_big = ops.CclWorkspace(S, S, MAX_COMPONENTS_LARGE, dev, slots=1)
-        big = self._ccl_big
-        ops.ccl(pred[b], output_p[b, 1], big, fg_sum=bufs["fg_sum"][b:b + 1], slot=0)
-        if self._mask_only:
-            bufs["lab256"][b].copy_(big.labels.view(S, S)[::4, ::4])
-        tab = big.tabs[0].cpu().numpy()
+    def _ccl_large(self, pred, pfg, fg_sum):
+        """One plane (pred uint8 [H,W], foreground probability pfg fp32 [H,W], its foreground count fg_sum int32 [1]) with more
+        connected components than the fast table holds: label it again with a MAX_COMPONENTS_LARGE table (synchronous, rare; one
+        workspace per plane size, shared by every caller). -> (workspace, host table); raises when even that table overflows."""
+        H, W = pred.shape
+        big = self.__dict__.setdefault("_ccl_big", {})      # (also called with a ProtoMedSAM as `self`)
+        if (H, W) not in big:
+            big[(H, W)] = ops.CclWorkspace(H, W, MAX_COMPONENTS_LARGE, pred.device, slots=1)
+        ws = ops.ccl(pred, pfg, big[(H, W)], fg_sum=fg_sum, slot=0)
+        tab = ws.tabs[0].cpu().numpy()
         if int(tab[0]) > int(tab[1]):
             raise RuntimeError(f"{int(tab[0])} connected components in one coarse mask exceed the table capacity "
                                f"{MAX_COMPONENTS_LARGE} (csrc/ccl.hip)")
-        return tab
+        return ws, tab
 
     def _side_stream(self, dev):
         if getattr(self, "_side", None) is None:
@@ -560,9 +559,6 @@ class ProtoSAM(nn.Module):
         """Reference contract (ProtoSAM.py:536-678): one query slice [1,3,H,W] -> (pred [H,W] float {0,1}, scores)."""
         if self.training:
             raise NotImplementedError("training-mode outputs (logits) are outside the inference hot path")
-        if self.coarse_pred_only:
-            output_logits = self._coarse_logits(query_image, coarse_model_input, degrees_rotate)
-            return self._coarse_only(output_logits, query_image.shape[-2])
         return self.forward_batch(query_image, coarse_model_input, degrees_rotate)[0]
 
     def _coarse_logits(self, query_images, coarse_model_input, degrees_rotate=0):
@@ -672,8 +668,11 @@ class ProtoSAM(nn.Module):
             overflow = int(tab[0]) > int(tab[1])
             if overflow:
                 # more components than the fast table holds (cv2 + the reference's per-component loop have no limit,
-                # util/utils.py:474-494, ProtoSAM.py:505): redo this slice with the large table
-                tab = self._ccl_overflow(b, bufs, output_p, pred, S)
+                # util/utils.py:474-494, ProtoSAM.py:505): redo this slice with the large table, and refresh what was derived
+                # from the truncated labelling
+                big, tab = self._ccl_large(pred[b], output_p[b, 1], bufs["fg_sum"][b:b + 1])
+                if self._mask_only:
+                    bufs["lab256"][b].copy_(big.labels.view(S, S)[::4, ::4])
             n_found, n = int(tab[0]), int(tab[1])
             stats.append(dict(n_components=n_found, fg_pixels=int(tab[2]), n_prompts=0))
             if n == 0:                                                          # ProtoSAM.py:612-613
@@ -695,14 +694,13 @@ class ProtoSAM(nn.Module):
                     # the fast path asked for the rings of the first MAX_NEG_COMPONENTS components of the fast table only (one
                     # tile grid per component): ask again for all of them, on the labelling the table in hand belongs to
                     # (the reference walks every component, ProtoSAM.py:395-419)
-                    big = n_found > MAX_COMPONENTS
-                    ws = self._ccl_big if big else cw
-                    neg_keys = ops.neg_points(ws, output_p[b, 0], ws.tabs[0] if big else cw.tabs[b], n,
-                                              labels=None if big else cw.labels_b[b]).cpu().numpy()
+                    ws = big if overflow else cw
+                    neg_keys = ops.neg_points(ws, output_p[b, 0], ws.tabs[0] if overflow else cw.tabs[b], n,
+                                              labels=None if overflow else cw.labels_b[b]).cpu().numpy()
             topk = None
             if self.num_points_for_sam > 1 and self.use_points and self.point_mode in (CONF_MODE, BOTH_MODE):
                 ids = [int(tab[3]) + 1] if self.use_cca else list(range(1, n + 1))
-                topk = self._topk_points(output_p[b, 1], self._ccl_big.labels if overflow else cw.labels_b[b], S, ids,
+                topk = self._topk_points(output_p[b, 1], big.labels if overflow else cw.labels_b[b], S, ids,
                                          self.num_points_for_sam)
             c, l, rows = self._prompts_from_table(tab, neg_keys, topk)
             spans.append((b, len(img_idx), len(l)))
@@ -794,15 +792,14 @@ class ProtoSAM(nn.Module):
         return results
 
     def _coarse_only_batch(self, output_logits, original_size):
-        """`_coarse_only` for B slices at once: one softmax / argmax launch, one connected-components chain, one copy of the
-        component tables to the host (round 5: forward_batch used to run SAM and drop its result when `coarse_pred_only` was set)."""
+        """ProtoSAM.py:580-590 (inference) for B slices at once: logits (bilinear to the query's size if they differ) -> one softmax /
+        argmax launch, one connected-components chain, one copy of the component tables to the host -> per slice the argmax map and
+        its mean fg confidence (get_confidence_from_logits); with CCA the best component and its confidence."""
         B = output_logits.shape[0]
-        if B == 1:
-            return [self._coarse_only(output_logits, original_size)]
         dev = output_logits.device
         H = int(original_size)
         key = (str(dev), H, B)
-        cache = self.__dict__.setdefault("_coarse_bufs", {})
+        cache = self.__dict__.setdefault("_coarse_bufs", {})     # (also called with a ProtoMedSAM as `self`)
         if key not in cache:
             while len(cache) >= 6:                   # (one set of buffers per batch size seen: keep the most recent few)
                 cache.pop(next(iter(cache)))
@@ -818,10 +815,10 @@ class ProtoSAM(nn.Module):
         tabs = cw.tabs[:B].cpu().numpy()
         out = []
         for b in range(B):
-            tab = tabs[b]
-            if int(tab[0]) > int(tab[1]):                        # more components than the fast table holds: the one-slice path's large table
-                out.append(self._coarse_only(output_logits[b:b + 1], original_size))
-                continue
+            tab, labels = tabs[b], cw.labels_b[b]
+            if int(tab[0]) > int(tab[1]):                        # more components than the fast table holds: see forward_batch
+                big, tab = self._ccl_large(pred[b], prob[b, 1], bufs["fg_sum"][b:b + 1])
+                labels = big.labels
             n = int(tab[1])
             rows = tab[ops.CC_HDR:ops.CC_HDR + ops.CC_STRIDE * n].reshape(n, ops.CC_STRIDE)
             if not self.use_cca:
@@ -830,39 +827,5 @@ class ProtoSAM(nn.Module):
                 out.append((pred[b].long() * 0, [0]))
             else:
                 k = int(tab[3])
-                out.append(((cw.labels_b[b].view(H, H) == (k + 1)).long(), [float(rows[k, 7])]))
+                out.append(((labels.view(H, H) == (k + 1)).long(), [float(rows[k, 7])]))
         return out
-
-    def _coarse_only(self, output_logits, original_size):
-        """ProtoSAM.py:580-590 (inference): logits (bilinear to the query's size if they differ) -> argmax map, mean fg
-        confidence (get_confidence_from_logits); optional CCA keeps the best component and reports its confidence."""
-        dev = output_logits.device
-        H = int(original_size)
-        key = (str(dev), H)
-        cache = self.__dict__.setdefault("_coarse_bufs", {})     # (also called with a ProtoMedSAM as `self`)
-        if key not in cache:
-            cache[key] = dict(fg_sum=torch.zeros(1, dtype=torch.int32, device=dev),
-                                   prob=torch.empty((1, 2, H, H), dtype=torch.float32, device=dev),
-                                   pred=torch.empty((1, H, H), dtype=torch.uint8, device=dev),
-                                   ccl=ops.CclWorkspace(H, H, MAX_COMPONENTS, dev, slots=1))
-        bufs = cache[key]
-        bufs["fg_sum"].zero_()
-        prob, pred = ops.prob_argmax(output_logits.float().contiguous(), H, H, prob=bufs["prob"], pred=bufs["pred"],
-                                     fg_sum=bufs["fg_sum"])
-        cw = ops.ccl(pred[0], prob[0, 1], bufs["ccl"], fg_sum=bufs["fg_sum"])
-        tab = cw.tab.cpu().numpy()
-        if int(tab[0]) > int(tab[1]):                            # more components than the fast table holds: see forward_batch
-            bufs["ccl_big"] = bufs.get("ccl_big") or ops.CclWorkspace(H, H, MAX_COMPONENTS_LARGE, dev, slots=1)
-            cw = ops.ccl(pred[0], prob[0, 1], bufs["ccl_big"], fg_sum=bufs["fg_sum"])
-            tab = cw.tab.cpu().numpy()
-            if int(tab[0]) > int(tab[1]):
-                raise RuntimeError(f"{int(tab[0])} connected components exceed the table capacity {MAX_COMPONENTS_LARGE}")
-        n = int(tab[1])
-        rows = tab[ops.CC_HDR:ops.CC_HDR + ops.CC_STRIDE * n].reshape(n, ops.CC_STRIDE)
-        if not self.use_cca:
-            return pred[0].long(), [float(rows[:, 7].sum())]
-        if n == 0:
-            return pred[0].long() * 0, [0]
-        k = int(tab[3])
-        keep = (cw.labels.view(H, H) == (k + 1)).long()
-        return keep, [float(rows[k, 7])]

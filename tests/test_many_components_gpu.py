@@ -127,7 +127,7 @@ def test_table_capacity_is_reported(dev, small_limits, monkeypatch):
 
 @pytest.mark.parametrize("use_cca", [False, True])
 def test_coarse_only_and_protomedsam_with_many_components(dev, small_limits, use_cca):
-    """The big-table fallbacks of `_coarse_only` (ProtoSAM.py:580-590) and of ProtoMedSAM (models/ProtoMedSAM.py:122-222)."""
+    """The big-table fallbacks of `_coarse_only_batch` (ProtoSAM.py:580-590) and of ProtoMedSAM (models/ProtoMedSAM.py:122-222)."""
     from oracle import glue
     from protosam_amd.grid_proto_fewshot import FewShotSeg
     from protosam_amd.protomedsam import ProtoMedSAM

@@ -47,7 +47,7 @@ def test_prob2_argmax_equals_chain(dev, IH):
     sc[3, :, 5:40, 7:50] = 0.25                                               # a tied patch inside a random plane
     P = sc.shape[0]
     sc = sc.contiguous().to(dev)
-    # the chain of the per-slice path (ProtoMedSAM.forward)
+    # the chain it replaces: resize, softmax + arg-max, softmax again (ProtoMedSAM.py:176-187, util/utils.py:485)
     full = ops.bilinear_nchw(sc, S, S) if IH != S else sc
     fg_ref = torch.zeros(P, dtype=torch.int32, device=dev)
     prob_ref, pred_ref = ops.prob_argmax(full.contiguous(), S, S, fg_sum=fg_ref)
