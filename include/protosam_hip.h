@@ -166,6 +166,12 @@ int psam_broadcast_rows(const float* row, int D, float* out, int B, long long st
  * util/utils.py:474-494 (the second softmax: util/utils.py:485). */
 int psam_prob2_argmax(const float* scores, int P, int IH, int IW, int OH, int OW, void* pred, float* pfg2, int* fg_sum,
                       float* prob, void* stream);
+/* psam_bilinear_nchw then psam_prob_argmax, for P planes in one launch, without the intermediate: grid-resolution class scores
+ * fp32 [P,2,GH,GW] -> bilinear to the image size IHxIW (models/grid_proto_fewshot.py:272-273) -> bilinear to OHxOW (skipped when
+ * equal) -> softmax -> prob fp32 [P,2,OH,OW] (both channels), argmax -> pred u8 [P,OH,OW], fg_sum int[P] (accumulated, caller
+ * zeroes; or NULL). Bit-identical to the two-launch chain. models/ProtoSAM.py:592-602 */
+int psam_scores_prob_argmax(const float* scores, int P, int GH, int GW, int IH, int IW, int OH, int OW, float* prob, void* pred,
+                            int* fg_sum, void* stream);
 /* per-image min/max (order-preserving uint32 pairs).  models/ProtoSAM.py:660 */
 int psam_minmax(const float* x, int B, long long n_per_img, void* mm, void* stream);
 /* ((x-min)/(max-min)*255).astype(uint8) -> (u8 - mean)/std -> im2col(16x16) half; mean3/std3 are HOST pointers.
@@ -292,6 +298,11 @@ int psam_mask_downscale(const float* masks, const float* wts, int n, int g, floa
  * (ProtoSAM.py:395-419; labels / tab as written by psam_ccl). key = float_bits(p_bg) << 32 | (0xFFFFFFFF - y*W - x); 0 = none. */
 int psam_neg_points(const int* labels, const float* pbg, const double* tab, int H, int W, int max_comp, int r, float thr,
                     unsigned long long* keys, void* stream);
+/* psam_neg_points for P planes in one launch (ProtoSAM.py:361-372,395-419 per (slice, class) plane): labels int32 [P,H,W] as
+ * psam_ccl_batch writes them, pbg fp32 with pbg_stride floats between planes, tabs fp64 [P][8 + 12*cap], keys [P][max_comp+1]
+ * (max_comp <= cap, P*(max_comp+1) <= 65535); plane p's keys are those of psam_neg_points on plane p. */
+int psam_neg_points_batch(const int* labels, const float* pbg, long long pbg_stride, const double* tabs, int cap, int P, int H,
+                          int W, int max_comp, int r, float thr, unsigned long long* keys, void* stream);
 
 /* Slice hand-off from a scan volume (raw NIfTI voxels [Z,H,W]; vol_dtype 0 int16, 1 float32, 2 uint8, 3 int32).
  * psam_volume_stats: out[0] = sum(x), out[1] = sum(x^2) in fp64, x = voxel*slope + inter  (MR_normalize / get_CT_statistics,

@@ -46,6 +46,7 @@ SIGNATURES = {
     "psam_prob_argmax": [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
     "psam_broadcast_rows": [c_void_p, c_int, c_void_p, c_int, c_longlong, c_longlong, c_void_p],
     "psam_prob2_argmax": [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    "psam_scores_prob_argmax": [c_void_p] + [c_int] * 7 + [c_void_p] * 4,
     "psam_minmax": [c_void_p, c_int, c_longlong, c_void_p, c_void_p],
     "psam_im2col3x3": [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p],
     "psam_cast_f16": [c_void_p, c_void_p, c_longlong, c_void_p],
@@ -80,6 +81,7 @@ SIGNATURES = {
     "psam_volume_slices": [c_void_p, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_int, c_int, c_int,
                            c_void_p, c_void_p],
     "psam_neg_points": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p],
+    "psam_neg_points_batch": [c_void_p, c_void_p, c_longlong, c_void_p] + [c_int] * 6 + [c_float, c_void_p, c_void_p],
     "psam_mask_downscale": [c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p],
     "psam_plane_stats": [c_void_p, c_int, c_int, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p],
     "psam_mask_binarize": [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p,

@@ -346,20 +346,27 @@ extern "C" int psam_ccl_batch(const void* pred, const float* pfg, long long pfg_
 //               r iterations of a 3x3 dilation = a (2r+1) x (2r+1) box (cv2.dilate(mask, ones(3,3), iterations=10), r = 10)
 // key = (float bits of p_bg) << 32 | (0xFFFFFFFF - pixel index): the maximum key is the largest p_bg, first pixel in raster
 // order on ties (torch.topk leaves tie order unspecified; same convention as the positive points); 0 = no such pixel.
-// One workgroup = one 32x32 tile of one component (blockIdx.z - 1) or of the global search (blockIdx.z == 0); tiles outside
-// the component's bounding box grown by r leave at once. Box dilation is separable: rows in LDS, then columns.
+// One workgroup = one 32x32 tile of one component (z - 1) or of the global search (z == 0) of one plane, blockIdx.z =
+// plane * (max_comp + 1) + z (psam_neg_points_batch: plane p's labels, p_bg, table and keys move by their plane strides;
+// psam_neg_points is the one-plane case); tiles outside the component's bounding box grown by r leave at once. Box dilation
+// is separable: rows in LDS, then columns.
 #define NP_T 32
 #define NP_RMAX 10
 __global__ __launch_bounds__(256) void neg_points_kernel(const int* __restrict__ labels, const float* __restrict__ pbg,
                                                          const double* __restrict__ tab, int H, int W, int r, float thr,
-                                                         unsigned long long* __restrict__ keys) {
+                                                         unsigned long long* __restrict__ keys, int nz, long long pbg_stride,
+                                                         long long tab_stride) {
   constexpr int TW = NP_T + 2 * NP_RMAX;
   __shared__ unsigned char m[TW][TW];
   __shared__ unsigned char hd[TW][NP_T];
   __shared__ unsigned long long red[4];
   const int t = threadIdx.x;
   const int x0 = blockIdx.x * NP_T, y0 = blockIdx.y * NP_T;
-  const int z = blockIdx.z;
+  const int plane = blockIdx.z / nz, z = blockIdx.z % nz;
+  labels += (size_t)plane * H * W;
+  pbg += (size_t)plane * pbg_stride;
+  tab += (size_t)plane * tab_stride;
+  keys += (size_t)plane * nz;
   unsigned long long best = 0ull;
   if (z == 0) {
     for (int i = t; i < NP_T * NP_T; i += 256) {
@@ -422,6 +429,20 @@ extern "C" int psam_neg_points(const int* labels, const float* pbg, const double
   if (H <= 0 || W <= 0 || max_comp < 0 || r < 0 || r > NP_RMAX) return PSAM_ERR_ARG;
   (void)hipMemsetAsync(keys, 0, sizeof(unsigned long long) * (max_comp + 1), (hipStream_t)stream);
   hipLaunchKernelGGL(neg_points_kernel, dim3((W + NP_T - 1) / NP_T, (H + NP_T - 1) / NP_T, max_comp + 1), dim3(256), 0,
-                     (hipStream_t)stream, labels, pbg, tab, H, W, r, thr, keys);
+                     (hipStream_t)stream, labels, pbg, tab, H, W, r, thr, keys, max_comp + 1, 0LL, 0LL);
+  return psam_launch_status();
+}
+
+// P planes in one launch: labels int32 [P,H,W] (psam_ccl_batch's), p_bg with `pbg_stride` floats between planes, tabs fp64
+// [P][8 + 12*cap], keys [P][max_comp+1]. Every plane asks for max_comp rings (component k >= its tab[1] leaves at once).
+extern "C" int psam_neg_points_batch(const int* labels, const float* pbg, long long pbg_stride, const double* tabs, int cap, int P,
+                                     int H, int W, int max_comp, int r, float thr, unsigned long long* keys, void* stream) {
+  if (H <= 0 || W <= 0 || P <= 0 || cap <= 0 || max_comp < 0 || max_comp > cap || r < 0 || r > NP_RMAX || pbg_stride < 0 ||
+      (long long)P * (max_comp + 1) > 65535 || !labels || !pbg || !tabs || !keys)
+    return PSAM_ERR_ARG;
+  (void)hipMemsetAsync(keys, 0, sizeof(unsigned long long) * (size_t)P * (max_comp + 1), (hipStream_t)stream);
+  hipLaunchKernelGGL(neg_points_kernel, dim3((W + NP_T - 1) / NP_T, (H + NP_T - 1) / NP_T, P * (max_comp + 1)), dim3(256), 0,
+                     (hipStream_t)stream, labels, pbg, tabs, H, W, r, thr, keys, max_comp + 1, pbg_stride,
+                     (long long)CC_HDR + (long long)CC_STRIDE * cap);
   return psam_launch_status();
 }

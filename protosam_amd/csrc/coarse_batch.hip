@@ -5,6 +5,12 @@
 //                        (models/ProtoMedSAM.py:176-187; util/utils.py:474-494, the second softmax at :485). What
 //                        psam_prob_argmax twice wrote as two [2,OH,OW] fp32 planes plus a second uint8 plane (26 MB per
 //                        1024^2 plane) is 5 MB here: the uint8 labels and the one fp32 plane psam_ccl_batch reads.
+//  psam_scores_prob_argmax : the same for ProtoSAM (models/ProtoSAM.py:592-602), which needs both softmax channels: P planes
+//                        of grid-resolution class scores [P,2,g,g] -> bilinear to the image size (IH,IW) (FewShotSeg.forward,
+//                        models/grid_proto_fewshot.py:272-273) -> bilinear to (OH,OW) -> softmax -> argmax. The [P,2,IH,IW]
+//                        intermediate is never written: each output pixel recomputes its four image-size samples from the
+//                        grid, with psam_bilinear_nchw's arithmetic, so prob / pred / fg_sum are the bits of psam_bilinear_nchw
+//                        followed by psam_prob_argmax.
 //  psam_mask_union_seg : every output mask of a batch of decoder calls in one launch: out[seg.o] = OR over the segment's
 //                        prompts of (up-sample -> > thr), nearest-resized MID -> OUT, as uint8 (models/ProtoMedSAM.py:49-60,
 //                        :219-220). Per segment the same bits as psam_mask_union + .to(torch.uint8).
@@ -130,6 +136,114 @@ extern "C" int psam_prob2_argmax(const float* scores, int P, int IH, int IW, int
   const int vec = (OW % 4 == 0) && ((uintptr_t)pred % 4 == 0) && ((uintptr_t)pfg2 % 16 == 0) && ((uintptr_t)prob % 16 == 0);
   hipLaunchKernelGGL(prob2_argmax_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, scores, P, IH, IW, OH, OW, per_block,
                      vec, (uint8_t*)pred, pfg2, prob, fg_sum);
+  return psam_launch_status();
+}
+
+// bilerp's expression as the two kernels this one replaces were compiled (fp-contract=fast lets the compiler choose which products
+// to fuse, and it chose differently for each): both fuse x.l0 * a into x.l1 * b; bilinear_nchw_kernel then rounds both row terms
+// (y.l0 * X + y.l1 * Y), prob_argmax_kernel fuses y.l0 * X into y.l1 * Y. Spelled out here with contraction off, so that this
+// kernel gives their bits whatever its own code shape.
+__device__ __forceinline__ float pb_lerp_nchw(const Lin& y, const Lin& x, float a, float b, float c, float d) {
+#pragma clang fp contract(off)
+  const float X = fmaf(x.l0, a, x.l1 * b), Y = fmaf(x.l0, c, x.l1 * d);
+  return y.l0 * X + y.l1 * Y;
+}
+__device__ __forceinline__ float pb_lerp_prob(const Lin& y, const Lin& x, float a, float b, float c, float d) {
+#pragma clang fp contract(off)
+  const float X = fmaf(x.l0, a, x.l1 * b), Y = fmaf(x.l0, c, x.l1 * d);
+  return fmaf(y.l0, X, y.l1 * Y);
+}
+
+// psam_bilinear_nchw's value at (y, x) of the (IH, IW) resize of the g x g plane `gp`: lin_src rows / columns, its blend
+__device__ __forceinline__ float pb_grid_sample(const float* __restrict__ gp, int GH, int GW, float gsh, float gsw, int y, int x) {
+  const Lin ly = lin_src(y, gsh, GH), lx = lin_src(x, gsw, GW);
+  const float* r0 = gp + (size_t)ly.i0 * GW;
+  const float* r1 = gp + (size_t)ly.i1 * GW;
+  return pb_lerp_nchw(ly, lx, r0[lx.i0], r0[lx.i1], r1[lx.i0], r1[lx.i1]);
+}
+
+// prob_argmax_kernel's per-pixel arithmetic (resample.hip) on logits that bilinear_nchw_kernel would have produced: the same
+// operations in the same order, the image-size samples computed instead of loaded.
+__global__ __launch_bounds__(256) void scores_prob_argmax_kernel(const float* __restrict__ scores, int P, int GH, int GW, int IH,
+                                                                 int IW, int OH, int OW, int per_block, int vec,
+                                                                 float* __restrict__ prob, uint8_t* __restrict__ pred,
+                                                                 int* __restrict__ fg_sum) {
+  __shared__ int wsum[4];
+  const int nch = (OW + PB_ROW - 1) / PB_ROW;
+  const long long per_plane = (long long)OH * nch;
+  const long long total = per_plane * P;
+  long long i = (long long)blockIdx.x * per_block;
+  const long long iend = min(i + (long long)per_block, total);
+  if (i >= iend) return;                                    // (uniform over the workgroup)
+  const bool same = (IH == OH && IW == OW);
+  const float gsh = (float)GH / (float)IH, gsw = (float)GW / (float)IW;   // psam_bilinear_nchw: grid -> image size
+  const float sh = (float)IH / (float)OH, sw = (float)IW / (float)OW;     // psam_prob_argmax: image size -> output
+  const size_t plane = (size_t)OH * OW;
+  int cur = (int)(i / per_plane), fgc = 0;
+  for (; i < iend; ++i) {
+    const int p = (int)(i / per_plane);
+    if (p != cur) {
+      if (fg_sum) pb_flush(fgc, fg_sum + cur, wsum);
+      fgc = 0;
+      cur = p;
+    }
+    const int rem = (int)(i - (long long)p * per_plane);
+    const int y = rem / nch;
+    const int x0 = (rem % nch) * PB_ROW + threadIdx.x * 4;
+    if (x0 >= OW) continue;
+    const float* g0p = scores + ((size_t)p * 2 + 0) * GH * GW;
+    const float* g1p = g0p + (size_t)GH * GW;
+    Lin ly = lin_src(y, sh, IH);
+    float p0v[4], p1v[4];
+    uint8_t fgv[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int x = min(x0 + k, OW - 1);
+      float l0, l1;
+      if (same) {
+        l0 = pb_grid_sample(g0p, GH, GW, gsh, gsw, y, x);
+        l1 = pb_grid_sample(g1p, GH, GW, gsh, gsw, y, x);
+      } else {
+        Lin lx = lin_src(x, sw, IW);
+        l0 = pb_lerp_prob(ly, lx, pb_grid_sample(g0p, GH, GW, gsh, gsw, ly.i0, lx.i0), pb_grid_sample(g0p, GH, GW, gsh, gsw, ly.i0, lx.i1),
+                    pb_grid_sample(g0p, GH, GW, gsh, gsw, ly.i1, lx.i0), pb_grid_sample(g0p, GH, GW, gsh, gsw, ly.i1, lx.i1));
+        l1 = pb_lerp_prob(ly, lx, pb_grid_sample(g1p, GH, GW, gsh, gsw, ly.i0, lx.i0), pb_grid_sample(g1p, GH, GW, gsh, gsw, ly.i0, lx.i1),
+                    pb_grid_sample(g1p, GH, GW, gsh, gsw, ly.i1, lx.i0), pb_grid_sample(g1p, GH, GW, gsh, gsw, ly.i1, lx.i1));
+      }
+      const float m = fmaxf(l0, l1);
+      const float e0 = expf(l0 - m), e1 = expf(l1 - m);
+      const float s = e0 + e1;
+      p0v[k] = e0 / s;
+      p1v[k] = e1 / s;
+      fgv[k] = p1v[k] > p0v[k] ? 1 : 0;  // argmax returns the first maximum on ties
+      if (x0 + k < OW) fgc += fgv[k];
+    }
+    const size_t o = (size_t)p * plane + (size_t)y * OW + x0;
+    const size_t o2 = (size_t)p * 2 * plane + (size_t)y * OW + x0;
+    if (vec && x0 + 3 < OW) {
+      *reinterpret_cast<float4*>(prob + o2) = make_float4(p0v[0], p0v[1], p0v[2], p0v[3]);
+      *reinterpret_cast<float4*>(prob + o2 + plane) = make_float4(p1v[0], p1v[1], p1v[2], p1v[3]);
+      *reinterpret_cast<uchar4*>(pred + o) = make_uchar4(fgv[0], fgv[1], fgv[2], fgv[3]);
+    } else {
+      for (int k = 0; k < 4 && x0 + k < OW; ++k) {
+        prob[o2 + k] = p0v[k];
+        prob[o2 + k + plane] = p1v[k];
+        pred[o + k] = fgv[k];
+      }
+    }
+  }
+  if (fg_sum) pb_flush(fgc, fg_sum + cur, wsum);
+}
+
+extern "C" int psam_scores_prob_argmax(const float* scores, int P, int GH, int GW, int IH, int IW, int OH, int OW, float* prob,
+                                       void* pred, int* fg_sum, void* stream) {
+  if (P <= 0 || GH <= 0 || GW <= 0 || IH <= 0 || IW <= 0 || OH <= 0 || OW <= 0 || !scores || !prob || !pred) return PSAM_ERR_ARG;
+  const long long items = (long long)P * OH * ((OW + PB_ROW - 1) / PB_ROW);
+  int per_block = 0;
+  const int grid = pb_grid(items, &per_block);
+  const int vec = (OW % 4 == 0) && ((uintptr_t)pred % 4 == 0) && ((uintptr_t)prob % 16 == 0);
+  hipLaunchKernelGGL(scores_prob_argmax_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, scores, P, GH, GW, IH, IW, OH, OW,
+                     per_block, vec, prob, (uint8_t*)pred, fg_sum);
   return psam_launch_status();
 }
 

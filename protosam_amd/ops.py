@@ -630,6 +630,30 @@ def prob2_argmax(scores, OH, OW, pred=None, pfg2=None, fg_sum=None, prob=None):
     return pred, pfg2
 
 
+def scores_prob_argmax(scores, IH, IW, OH, OW, prob=None, pred=None, fg_sum=None):
+    """scores fp32 [P,2,g,g] (grid resolution) -> (prob fp32 [P,2,OH,OW], pred uint8 [P,OH,OW]) in one launch
+    (psam_scores_prob_argmax): bilinear to the image size (IH,IW), bilinear to (OH,OW) unless equal, softmax, argmax - the bits of
+    `prob_argmax(bilinear_nchw(scores, IH, IW), OH, OW)` without the [P,2,IH,IW] intermediate. fg_sum int32 [P] is accumulated
+    (zero it first)."""
+    _req(scores, torch.float32, "scores")
+    assert scores.is_contiguous() and scores.dim() == 4 and scores.shape[1] == 2
+    P, dev = scores.shape[0], scores.device
+    if prob is None:
+        prob = torch.empty((P, 2, OH, OW), dtype=torch.float32, device=dev)
+    if pred is None:
+        pred = torch.empty((P, OH, OW), dtype=torch.uint8, device=dev)
+    _req(prob, torch.float32, "prob")
+    assert prob.is_contiguous() and prob.numel() >= P * 2 * OH * OW
+    assert pred.dtype == torch.uint8 and pred.is_cuda and pred.is_contiguous() and pred.numel() >= P * OH * OW
+    assert fg_sum is None or (fg_sum.dtype == torch.int32 and fg_sum.is_cuda and fg_sum.is_contiguous() and fg_sum.numel() >= P)
+    h = _tstart("scores_prob_argmax")
+    st = _lib.lib().psam_scores_prob_argmax(_ptr(scores), P, scores.shape[2], scores.shape[3], IH, IW, OH, OW, _ptr(prob),
+                                            _ptr(pred), _ptr(fg_sum), _stream())
+    _tstop(h, P * (2 * scores.shape[2] * scores.shape[3] * 4 + OH * OW * 9))
+    _lib.check(st, "psam_scores_prob_argmax")
+    return prob, pred
+
+
 def broadcast_rows(row, out, B, stride, off):
     _req(row, torch.float32, "row"); _req(out, torch.float32, "out")
     st = _lib.lib().psam_broadcast_rows(_ptr(row), row.numel(), _ptr(out), B, stride, off, _stream())
@@ -1177,6 +1201,26 @@ def neg_points(ws, pbg, tab, max_comp, r=10, thr=0.95, keys=None, labels=None):
     st = _lib.lib().psam_neg_points(_ptr(ws.labels if labels is None else labels), _ptr(pbg), _ptr(tab), ws.H, ws.W, max_comp, r,
                                    float(thr), _ptr(keys), _stream())
     _lib.check(st, "psam_neg_points")
+    return keys
+
+
+def neg_points_batch(labels, pbg, tabs, max_comp, r=10, thr=0.95, keys=None):
+    """`neg_points` for P planes in one launch (psam_neg_points_batch): labels int32 [P,H*W] or [P,H,W] (psam_ccl_batch's,
+    e.g. ws.labels_b[:P]), p_bg fp32 [P,H,W] view with any plane stride (channel 0 of a [P,2,H,W] probability map), tabs fp64
+    [P, 8 + 12*cap] -> int64 keys [P, max_comp+1], row p = `neg_points` of plane p."""
+    _req(pbg, torch.float32, "pbg")
+    assert labels.dtype == torch.int32 and labels.is_cuda and labels.is_contiguous()
+    assert tabs.dtype == torch.float64 and tabs.is_cuda and tabs.is_contiguous() and tabs.dim() == 2
+    P, H, W = pbg.shape
+    assert pbg.stride(1) == W and labels.numel() == P * H * W and tabs.shape[0] == P
+    assert (tabs.shape[1] - CC_HDR) % CC_STRIDE == 0
+    cap = (tabs.shape[1] - CC_HDR) // CC_STRIDE
+    if keys is None:
+        keys = torch.empty((P, max_comp + 1), dtype=torch.int64, device=pbg.device)
+    assert keys.dtype == torch.int64 and keys.is_contiguous() and keys.numel() >= P * (max_comp + 1)
+    st = _lib.lib().psam_neg_points_batch(_ptr(labels), _ptr(pbg), pbg.stride(0), _ptr(tabs), cap, P, H, W, max_comp, r,
+                                          float(thr), _ptr(keys), _stream())
+    _lib.check(st, "psam_neg_points_batch")
     return keys
 
 

@@ -55,6 +55,38 @@ DECODER_CHUNK = 256           # prompt sets per decoder call (workspace ~ 25 MB 
 MAX_NEG_COMPONENTS = 64   # psam_neg_points launches one tile grid per component
 
 
+CCL_SLOTS = 32            # planes per connected-components launch chain of forward_classes_batch (~8 MB of scratch per slot)
+
+
+def plan_class_prompts(B, C, plane_sets, feat_row):
+    """Host bookkeeping of `ProtoSAM.forward_classes_batch` (no device work). plane_sets: {(b, c): (coords or None, labels)}, the
+    prompt sets of slice b, class c in table order (coords None for mask prompts, where labels are component ids); feat_row[b]:
+    the row of the encoder output that holds slice b (-1: not encoded). Decoder rows run slice-major, then class, then set.
+    -> dict(prompt={(b, c): first row}, spans={(b, c): (first row, number of sets)}, coords, labels, img_idx (encoder row per
+    decoder row), plane_idx (class-major plane c*B + b per decoder row), segs int32 [B*C, 3] = (first row, count, b*C + c): one
+    psam_mask_union_seg segment per (slice, class) of a [B, C, H, W] output, count 0 (zeros) where a pair has no prompt)."""
+    prompt, spans, coords, labels, img_idx, plane_idx = {}, {}, [], [], [], []
+    segs = np.zeros((B * C, 3), dtype=np.int32)
+    for b in range(B):
+        for c in range(C):
+            o = b * C + c
+            segs[o] = (0, 0, o)
+            cs, ls = plane_sets.get((b, c), (None, ()))
+            if not len(ls):
+                continue
+            if feat_row[b] < 0:
+                raise ValueError(f"slice {b} has prompts but no image embedding")
+            first = len(labels)
+            prompt[(b, c)], spans[(b, c)] = first, (first, len(ls))
+            if cs is not None:
+                coords += cs
+            labels += ls
+            img_idx += [feat_row[b]] * len(ls)
+            plane_idx += [c * B + b] * len(ls)
+            segs[o] = (first, len(ls), o)
+    return dict(prompt=prompt, spans=spans, coords=coords, labels=labels, img_idx=img_idx, plane_idx=plane_idx, segs=segs)
+
+
 class StageTimer:
     """Optional per-stage GPU timing of `forward_batch` (bench.py): HIP events on the launch stream at the stage boundaries;
     the time between two consecutive marks is booked on the later one. Off (None) by default: no events are recorded."""
@@ -713,29 +745,7 @@ class ProtoSAM(nn.Module):
             # 6m. mask prompts: dense embedding per component, no sparse prompts, best of the three masks
             #     (get_sam_input_mask :452-466, predict_w_masks :468-498)
             P = len(labels)
-            pe = sam.prompt_encoder._packed()
-            dpk = sam.mask_decoder._packed()
-            iop = torch.tensor(img_idx, dtype=torch.int64).to(dev, non_blocking=True)
-            ids = torch.tensor(labels, dtype=torch.int32).to(dev, non_blocking=True)
-            fg, bg = self._mask_vals
-            sop = torch.tensor(slice_idx, dtype=torch.int64).to(dev, non_blocking=True)
-            masks = torch.empty((P, 4, 256, 256), dtype=torch.float32, device=dev)
-            iou = torch.empty((P, 4), dtype=torch.float32, device=dev)
-            zero_dense = torch.zeros(256, dtype=torch.float32, device=dev)
-            for c0 in range(0, P, DECODER_CHUNK):
-                # the dense prompt embedding and the decoder's image operand are [chunk, 4096, 256] fp32 (4 MiB per prompt set
-                # each): built per chunk, so that memory stays bounded however many components a slice has
-                c1 = min(c0 + DECODER_CHUNK, P)
-                prompt = torch.where(bufs["lab256"][sop[c0:c1]] == ids[c0:c1, None, None], fg, bg).to(torch.float32)
-                dense = sam.prompt_encoder.embed_masks_tokens(prompt[:, None])           # [chunk, 4096, 256]
-                src = (feat_tok[iop[c0:c1]] + dense).contiguous()                         # mask_decoder.py:126-127
-                del dense
-                tokens = dpk["out_tok"].unsqueeze(0).expand(c1 - c0, -1, -1).contiguous()
-                sam.mask_decoder.predict_masks_tokens(
-                    src, pe["pe_tok"], tokens, zero_dense,
-                    img_of_prompt=torch.arange(c1 - c0, dtype=torch.int32, device=dev), masks_out=masks[c0:c1],
-                    iou_out=iou[c0:c1])
-                del src
+            masks, iou = self._decode_mask_sets(feat_tok, bufs["lab256"], slice_idx, labels, img_idx)
             best = iou[:, 1:].argmax(dim=1)                                               # score.argmax(), :494
             chosen = masks[torch.arange(P, device=dev), best + 1].unsqueeze(1).contiguous()   # [P,1,256,256]
             iou_host = iou[:, 1:].max(dim=1).values.cpu().numpy()
@@ -744,38 +754,8 @@ class ProtoSAM(nn.Module):
                 results[b] = (out, [np.float32(v) for v in iou_host[start:start + cnt]])
             self.last_stats.update(low_res=masks, iou=iou, best=best, spans=spans)
         elif spans:
-            P = len(labels)
-            pe = sam.prompt_encoder._packed()
-            dpk = sam.mask_decoder._packed()
-            iop_all = torch.tensor(img_idx, dtype=torch.int32).to(dev, non_blocking=True)
-            # 6. batched two-way decoder over all components of all slices (ProtoSAM.py:500-527); prompt sets of equal
-            #    length share a batch (they differ only when some component has no ring / no global negative point)
-            groups = {}
-            for i, lab in enumerate(labels):
-                groups.setdefault(len(lab), []).append(i)
-            masks = iou = None
-            for Ns, idx in groups.items():
-                cg = np.asarray([coords[i] for i in idx], dtype=np.float64).astype(np.float32).reshape(len(idx), Ns, 2)
-                lg = np.asarray([labels[i] for i in idx], dtype=np.int32).reshape(len(idx), Ns)
-                tokens = ops.prompt_tokens(torch.from_numpy(cg).to(dev, non_blocking=True),
-                                           torch.from_numpy(lg).to(dev, non_blocking=True), pe["G"], pe["type_emb"],
-                                           dpk["out_tok"], len(idx), Ns, float(S))
-                if len(groups) == 1 and P <= DECODER_CHUNK:
-                    masks, iou, _ = sam.mask_decoder.predict_masks_tokens(feat_tok, pe["pe_tok"], tokens, pe["no_mask"],
-                                                                          img_of_prompt=iop_all)
-                else:
-                    if masks is None:
-                        masks = torch.empty((P, 4, 256, 256), dtype=torch.float32, device=dev)
-                        iou = torch.empty((P, 4), dtype=torch.float32, device=dev)
-                    it = torch.tensor(idx, dtype=torch.int64, device=dev)
-                    iop_g = iop_all[it].contiguous()
-                    for c0 in range(0, len(idx), DECODER_CHUNK):      # bounded decoder workspace however many components
-                        c1 = min(c0 + DECODER_CHUNK, len(idx))
-                        m_g, i_g, _ = sam.mask_decoder.predict_masks_tokens(
-                            feat_tok, pe["pe_tok"], tokens[c0:c1].contiguous(), pe["no_mask"],
-                            img_of_prompt=iop_g[c0:c1].contiguous())
-                        masks[it[c0:c1]] = m_g
-                        iou[it[c0:c1]] = i_g
+            # 6. batched two-way decoder over all components of all slices (ProtoSAM.py:500-527)
+            masks, iou = self._decode_point_sets(feat_tok, coords, labels, img_idx)
             sel = 0 if self.use_cca else 1                                      # multimask_output = not use_cca; index 0
             _mark("prompt encoder + mask decoder")
             iou_host = iou[:, sel].cpu().numpy()
@@ -790,6 +770,265 @@ class ProtoSAM(nn.Module):
             else:
                 self.last_stats.update(low_res=masks, iou=iou, sel=sel, spans=spans)
         return results
+
+    def _class_bufs(self, dev, P, B):
+        """Buffers of `forward_classes_batch`, grown to the largest P (planes) / B (slices) seen: per plane both softmax channels,
+        the arg-max map, the foreground count, the component table (pinned), the negative-point keys and 256^2 labels; per slice
+        the encoder input (`_sam_features`' keys)."""
+        S = self.sam.image_encoder.img_size
+        cb = self.__dict__.setdefault("_cbufs", {})
+        if cb.get("P", 0) < P:
+            cb.update(P=P, prob=None, pred=None, lab256=None)      # (drop the old planes before allocating the larger ones)
+            cb.update(prob=torch.empty((P, 2, S, S), dtype=torch.float32, device=dev),
+                      pred=torch.empty((P, S, S), dtype=torch.uint8, device=dev),
+                      fg_sum=torch.zeros(P, dtype=torch.int32, device=dev), fg_host=torch.zeros(P, dtype=torch.int32).pin_memory(),
+                      tabs_host=torch.empty((P, ops.CC_HDR + ops.CC_STRIDE * MAX_COMPONENTS), dtype=torch.float64).pin_memory(),
+                      neg_keys=torch.empty((P, MAX_NEG_COMPONENTS + 1), dtype=torch.int64, device=dev),
+                      neg_keys_host=torch.empty((P, MAX_NEG_COMPONENTS + 1), dtype=torch.int64).pin_memory(),
+                      lab256=torch.empty((P, S // 4, S // 4), dtype=torch.int32, device=dev) if self._mask_only else None,
+                      fg_event=torch.cuda.Event(), event=torch.cuda.Event())
+        if cb.get("B", 0) < B:
+            cb.update(B=B, q1024=None, patches=None)
+            cb.update(q1024=torch.empty((B, 3, S, S), dtype=torch.float32, device=dev),
+                      mm=torch.empty(2 * B, dtype=torch.int32, device=dev),
+                      patches=torch.empty((B * 4096, 768), dtype=torch.float16, device=dev))
+        slots = min(P, CCL_SLOTS)
+        if getattr(self, "_ccl_chunk", None) is None or self._ccl_chunk.slots < slots:
+            self._ccl_chunk = None
+            self._ccl_chunk = ops.CclWorkspace(S, S, MAX_COMPONENTS, dev, slots=slots)
+        return cb
+
+    def _plane_prompts(self, p, tab, labels, pbg, pfg, neg_keys, ws=None, slot=0):
+        """One plane's prompt sets from its component table, as `forward_batch` builds them for a slice: `labels` / `ws` the
+        labelling the table belongs to (ws, slot: its workspace and table row, for negative points beyond the fast key rows),
+        pbg / pfg its softmax channels, neg_keys its fast negative-point keys. -> (coords or None, labels)."""
+        S = self.sam.image_encoder.img_size
+        n_found, n = int(tab[0]), int(tab[1])
+        ids = [int(tab[3]) + 1] if self.use_cca else list(range(1, n + 1))
+        if self._mask_only:
+            return None, ids
+        if self.use_neg_points and (n > MAX_NEG_COMPONENTS or n_found > MAX_COMPONENTS):
+            # the rings of all n components (the fast keys hold the first MAX_NEG_COMPONENTS; forward_batch does the same)
+            neg_keys = ops.neg_points(ws, pbg, ws.tabs[slot], n, labels=labels).cpu().numpy()
+        topk = None
+        if self.num_points_for_sam > 1 and self.use_points and self.point_mode in (CONF_MODE, BOTH_MODE):
+            topk = self._topk_points(pfg, labels, S, ids, self.num_points_for_sam)
+        c, l, _ = self._prompts_from_table(tab, neg_keys, topk)
+        return c, l
+
+    @torch.no_grad()
+    def forward_classes_batch(self, query_images, support_image, support_masks, val_wsize=2, out=None, degrees_rotate=0):
+        """The multi-class path (validation_protosam.py runs one 1-way episode per organ on the same slices): B query slices
+        [B,3,H,W] x C classes (support_masks: C masks of ONE support image) in one call. Returns results[b][c] = (mask, scores),
+        what `forward(query_images[b:b+1], ALPNetInput(support_image, [support_masks[c]], ...))` gives: the masks are uint8 views
+        of one [B,C,H,W] tensor (`out` if given), zeros and [0] for a pair whose coarse mask is empty.
+        Pipeline: ONE DINOv2 forward of the B slices matched against the C banks (FewShotSeg.class_scores, class-major planes
+        c*B + b at grid resolution) -> ONE psam_scores_prob_argmax over the P = C*B planes (both resizes, softmax, arg-max) ->
+        connected components in chunks of CCL_SLOTS planes, each chunk's negative points (psam_neg_points_batch), 256^2 labels and
+        table taken before the next chunk overwrites its labels -> ONE SAM encoder forward of the slices where some class has
+        foreground -> the prompt sets of every (slice, class) -> the batched decoder -> ONE psam_mask_union_seg into [B,C,H,W].
+        `last_stats`: prompt / spans ((b, c) -> rows of low_res), prompts ((b, c) -> its prompt sets), n_prompted, n_encoded,
+        n_components [B][C], low_res, iou, sel."""
+        if self.training:
+            raise NotImplementedError("training-mode outputs (logits) are outside the inference hot path")
+        if degrees_rotate != 0:
+            raise NotImplementedError("forward_classes_batch: rotation TTA (degrees_rotate != 0); use forward_batch per class")
+        if isinstance(support_image, (list, tuple)):
+            if any(isinstance(x, (list, tuple)) for x in support_image):
+                raise NotImplementedError("forward_classes_batch: one support image per call (mixed supports); call once per support")
+            if len(support_image) != 1:
+                raise NotImplementedError("forward_classes_batch: one support shot (multi-shot support)")
+            support_image = support_image[0]
+        if support_image.dim() != 4 or support_image.shape[0] != 1:
+            raise NotImplementedError("forward_classes_batch: one support shot [1,3,H,W] (multi-shot support)")
+        if any(isinstance(m, (list, tuple)) for m in support_masks):
+            raise NotImplementedError("forward_classes_batch: one support mask per class (multi-shot support)")
+        alp = getattr(self.coarse_segmentation_model, "model", None)
+        if not hasattr(alp, "class_scores"):
+            raise TypeError("forward_classes_batch needs a coarse model with class_scores (ALPNetWrapper(FewShotSeg))")
+        sc = alp.class_scores(support_image, support_masks, query_images, isval=True, val_wsize=val_wsize)   # [C,B,2,g,g]
+        C, B, gh, gw = sc.shape[0], sc.shape[1], sc.shape[-2], sc.shape[-1]
+        P = C * B
+        sc = sc.view(P, 2, gh, gw)
+        IH, IW = support_image.shape[-2:]              # the image size FewShotSeg.forward resizes its logits to
+        H = query_images.shape[-2]
+        dev = query_images.device
+        if self.coarse_pred_only:                       # ProtoSAM.py:580-590 per plane
+            res = self._coarse_only_batch(ops.bilinear_nchw(sc.contiguous(), IH, IW), H)
+            self.last_stats = dict(n_slices=B, n_classes=C)
+            return [[res[c * B + b] for c in range(C)] for b in range(B)]
+        sam = self.sam
+        S = sam.image_encoder.img_size
+        cb = self._class_bufs(dev, P, B)
+        prob, pred, fg = cb["prob"][:P], cb["pred"][:P], cb["fg_sum"][:P]
+        # 1. bilinear to the image size -> bilinear to 1024 -> softmax -> argmax, every plane in one launch   ProtoSAM.py:592-602
+        fg.zero_()
+        ops.scores_prob_argmax(sc.contiguous(), IH, IW, S, S, prob=prob, pred=pred, fg_sum=fg)
+        cb["fg_host"][:P].copy_(fg, non_blocking=True)
+        cb["fg_event"].record()
+        # 2. connected components in chunks of planes; whatever reads a chunk's labels runs before the next chunk overwrites them
+        cw = self._ccl_chunk
+        need_topk = self.num_points_for_sam > 1 and self.use_points and self.point_mode in (CONF_MODE, BOTH_MODE)
+        tabs_h, keys_h = cb["tabs_host"][:P], cb["neg_keys_host"][:P]
+        plane_sets, found, slow = {}, [0] * P, set()
+        for c0 in range(0, P, cw.slots):
+            c1 = min(c0 + cw.slots, P)
+            n = c1 - c0
+            ops.ccl_batch(pred[c0:c1], prob[c0:c1], cw, fg_sum=fg[c0:c1])
+            if self.use_neg_points:
+                ops.neg_points_batch(cw.labels_b[:n], prob[c0:c1, 0], cw.tabs[:n], MAX_NEG_COMPONENTS, keys=cb["neg_keys"][c0:c1])
+                keys_h[c0:c1].copy_(cb["neg_keys"][c0:c1], non_blocking=True)
+            if self._mask_only:   # cv2.resize(mask, (256, 256), INTER_NEAREST) samples pixel (4y, 4x): one copy per chunk
+                cb["lab256"][c0:c1].copy_(cw.labels_b[:n].view(n, S, S)[:, ::4, ::4])
+            tabs_h[c0:c1].copy_(cw.tabs[:n], non_blocking=True)
+            if need_topk or self.use_neg_points:
+                # host top-k and the negative points of planes beyond the fast key rows read this chunk's labels: now
+                cb["event"].record()
+                cb["event"].synchronize()
+                for i in range(n):
+                    p = c0 + i
+                    tab = tabs_h[p].numpy()
+                    if int(tab[0]) > int(tab[1]) or int(tab[1]) == 0:
+                        continue                        # (overflow: relabelled below; empty: no prompt)
+                    b, c = p % B, p // B
+                    plane_sets[(b, c)] = self._plane_prompts(p, tab, cw.labels_b[i], prob[p, 0], prob[p, 1], keys_h[p].numpy(),
+                                                             cw, i)
+                    slow.add(p)
+        cb["event"].record()
+        # 3. SAM image encoder on the slices where some class has foreground (ProtoSAM.py:612-613 returns before set_image for
+        #    an empty coarse mask), enqueued before the host waits for the tables
+        cb["fg_event"].synchronize()
+        fgh = cb["fg_host"][:P].view(C, B)
+        keep = [b for b in range(B) if int(fgh[:, b].max()) > 0]
+        feat_row, feat_tok = [-1] * B, None
+        if keep:
+            sub = query_images if len(keep) == B else query_images[torch.tensor(keep, device=dev)]
+            feat_tok = self._sam_features(sub, cb, len(keep), S)
+            for i, b in enumerate(keep):
+                feat_row[b] = i
+        # 4. host: the prompt sets of every (slice, class)
+        cb["event"].synchronize()
+        for p in range(P):
+            b, c = p % B, p // B
+            tab = tabs_h[p].numpy()
+            found[p] = int(tab[0])
+            if p in slow:
+                continue
+            if int(tab[0]) > int(tab[1]):
+                # more components than the fast table holds: this plane again with the large table, as forward_batch does
+                big, tab = self._ccl_large(pred[p], prob[p, 1], fg[p:p + 1])
+                if self._mask_only:
+                    cb["lab256"][p].copy_(big.labels.view(S, S)[::4, ::4])
+                if int(tab[1]) > 0:
+                    plane_sets[(b, c)] = self._plane_prompts(p, tab, big.labels, prob[p, 0], prob[p, 1], None, big, 0)
+                continue
+            if int(tab[1]) == 0:
+                continue
+            plane_sets[(b, c)] = self._plane_prompts(p, tab, None, prob[p, 0], prob[p, 1], None)   # (no labels needed here)
+        plan = plan_class_prompts(B, C, plane_sets, feat_row)
+        # 5. the batched decoder over every (slice, class) prompt set
+        masks = iou = None
+        sel = 0 if self.use_cca else 1                  # multimask_output = not use_cca; index 0
+        if plan["labels"]:
+            if self._mask_only:
+                masks, iou = self._decode_mask_sets(feat_tok, cb["lab256"], plan["plane_idx"], plan["labels"], plan["img_idx"])
+                best = iou[:, 1:].argmax(dim=1)                                               # score.argmax(), :494
+                low = masks[torch.arange(len(plan["labels"]), device=dev), best + 1].unsqueeze(1).contiguous()
+                scores_h = iou[:, 1:].max(dim=1).values.cpu().numpy()
+                sel_u = 0
+            else:
+                masks, iou = self._decode_point_sets(feat_tok, plan["coords"], plan["labels"], plan["img_idx"])
+                low, sel_u = masks, sel
+                scores_h = iou[:, sel].cpu().numpy()
+        # 6. upsample -> threshold -> union over each pair's prompts -> nearest to the input size, into [B,C,H,W]
+        if out is None:
+            out = torch.empty((B, C, H, H), dtype=torch.uint8, device=dev)
+        assert out.shape == (B, C, H, H) and out.dtype == torch.uint8 and out.is_contiguous()
+        segs = torch.from_numpy(plan["segs"]).to(dev)
+        if plan["labels"]:
+            ops.mask_union_seg(low, sel_u, segs, P, S, H, sam.variant_id(), sam.mask_threshold, out=out.view(P, H, H))
+        else:
+            ops.mask_union_seg(None, 0, segs, P, S, H, sam.variant_id(), sam.mask_threshold, out=out.view(P, H, H))
+        results = [[(out[b, c], [0]) for c in range(C)] for b in range(B)]
+        for (b, c), (first, cnt) in plan["spans"].items():
+            results[b][c] = (out[b, c], [np.float32(v) for v in scores_h[first:first + cnt]])
+        self.last_stats = dict(n_slices=B, n_classes=C, prompt=plan["prompt"], spans=plan["spans"], n_prompted=len(plan["prompt"]),
+                               n_encoded=len(keep), n_components=[[found[c * B + b] for c in range(C)] for b in range(B)],
+                               prompts=plane_sets, low_res=masks, iou=iou, sel=sel)
+        if self._mask_only and masks is not None:
+            self.last_stats.update(best=best)
+        return results
+
+    def _decode_point_sets(self, feat_tok, coords, labels, img_idx):
+        """Point / box prompt sets (`_prompts_from_table`'s coords and labels, one set per row) on image img_idx[i] of feat_tok
+        through the batched two-way decoder (ProtoSAM.py:500-527). Sets of equal length share a batch (they differ only when some
+        component has no ring / no global negative point), chunked by DECODER_CHUNK. -> low-res masks [n,4,256,256], iou [n,4]."""
+        sam = self.sam
+        S = sam.image_encoder.img_size
+        dev = feat_tok.device
+        P = len(labels)
+        pe = sam.prompt_encoder._packed()
+        dpk = sam.mask_decoder._packed()
+        iop_all = torch.tensor(img_idx, dtype=torch.int32).to(dev, non_blocking=True)
+        groups = {}
+        for i, lab in enumerate(labels):
+            groups.setdefault(len(lab), []).append(i)
+        masks = iou = None
+        for Ns, idx in groups.items():
+            cg = np.asarray([coords[i] for i in idx], dtype=np.float64).astype(np.float32).reshape(len(idx), Ns, 2)
+            lg = np.asarray([labels[i] for i in idx], dtype=np.int32).reshape(len(idx), Ns)
+            tokens = ops.prompt_tokens(torch.from_numpy(cg).to(dev, non_blocking=True),
+                                       torch.from_numpy(lg).to(dev, non_blocking=True), pe["G"], pe["type_emb"],
+                                       dpk["out_tok"], len(idx), Ns, float(S))
+            if len(groups) == 1 and P <= DECODER_CHUNK:
+                masks, iou, _ = sam.mask_decoder.predict_masks_tokens(feat_tok, pe["pe_tok"], tokens, pe["no_mask"],
+                                                                      img_of_prompt=iop_all)
+            else:
+                if masks is None:
+                    masks = torch.empty((P, 4, 256, 256), dtype=torch.float32, device=dev)
+                    iou = torch.empty((P, 4), dtype=torch.float32, device=dev)
+                it = torch.tensor(idx, dtype=torch.int64, device=dev)
+                iop_g = iop_all[it].contiguous()
+                for c0 in range(0, len(idx), DECODER_CHUNK):      # bounded decoder workspace however many components
+                    c1 = min(c0 + DECODER_CHUNK, len(idx))
+                    m_g, i_g, _ = sam.mask_decoder.predict_masks_tokens(
+                        feat_tok, pe["pe_tok"], tokens[c0:c1].contiguous(), pe["no_mask"],
+                        img_of_prompt=iop_g[c0:c1].contiguous())
+                    masks[it[c0:c1]] = m_g
+                    iou[it[c0:c1]] = i_g
+        return masks, iou
+
+    def _decode_mask_sets(self, feat_tok, lab256, plane_idx, ids, img_idx):
+        """Mask prompts (get_sam_input_mask :452-466, predict_w_masks :468-498): prompt i is component ids[i] of the 256^2 label
+        plane lab256[plane_idx[i]], as a dense embedding, no sparse prompts, on image img_idx[i] of feat_tok.
+        -> low-res masks [n,4,256,256], iou [n,4] (the caller keeps the best of masks 1-3)."""
+        sam = self.sam
+        dev = feat_tok.device
+        P = len(ids)
+        pe = sam.prompt_encoder._packed()
+        dpk = sam.mask_decoder._packed()
+        iop = torch.tensor(img_idx, dtype=torch.int64).to(dev, non_blocking=True)
+        ids = torch.tensor(ids, dtype=torch.int32).to(dev, non_blocking=True)
+        fg, bg = self._mask_vals
+        sop = torch.tensor(plane_idx, dtype=torch.int64).to(dev, non_blocking=True)
+        masks = torch.empty((P, 4, 256, 256), dtype=torch.float32, device=dev)
+        iou = torch.empty((P, 4), dtype=torch.float32, device=dev)
+        zero_dense = torch.zeros(256, dtype=torch.float32, device=dev)
+        for c0 in range(0, P, DECODER_CHUNK):
+            # the dense prompt embedding and the decoder's image operand are [chunk, 4096, 256] fp32 (4 MiB per prompt set
+            # each): built per chunk, so that memory stays bounded however many components a slice has
+            c1 = min(c0 + DECODER_CHUNK, P)
+            prompt = torch.where(lab256[sop[c0:c1]] == ids[c0:c1, None, None], fg, bg).to(torch.float32)
+            dense = sam.prompt_encoder.embed_masks_tokens(prompt[:, None])           # [chunk, 4096, 256]
+            src = (feat_tok[iop[c0:c1]] + dense).contiguous()                         # mask_decoder.py:126-127
+            del dense
+            tokens = dpk["out_tok"].unsqueeze(0).expand(c1 - c0, -1, -1).contiguous()
+            sam.mask_decoder.predict_masks_tokens(
+                src, pe["pe_tok"], tokens, zero_dense,
+                img_of_prompt=torch.arange(c1 - c0, dtype=torch.int32, device=dev), masks_out=masks[c0:c1],
+                iou_out=iou[c0:c1])
+            del src
+        return masks, iou
 
     def _coarse_only_batch(self, output_logits, original_size):
         """ProtoSAM.py:580-590 (inference) for B slices at once: logits (bilinear to the query's size if they differ) -> one softmax /

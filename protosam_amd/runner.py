@@ -107,8 +107,9 @@ def run_slices(model, vol, sup_imgs, sup_masks, zs, device, out=None, batch=1, m
 @torch.no_grad()
 def run_slices_classes(model, vol, sup_imgs, sup_masks_per_part, zs, device, batch=16, out=None):
     """The multi-class form of `run_slices` (BASELINE config 5; the reference runs one 1-way episode per class, validation.py:207):
-    slices `zs` of `vol` [n,S,S] against C classes, `batch` slices per `model.forward_classes_batch` call (a ProtoMedSAM). Part p
-    of the scan has its own support image sup_imgs[p] and C masks sup_masks_per_part[p]; batches are cut at part boundaries.
+    slices `zs` of `vol` [n,S,S] against C classes, `batch` slices per `model.forward_classes_batch` call (a ProtoMedSAM or a
+    ProtoSAM). Part p of the scan has its own support image sup_imgs[p] and C masks sup_masks_per_part[p]; batches are cut at part
+    boundaries.
     Returns uint8 masks [len(zs), C, S, S] (the batch's output tensor is a slice of it) and the number of prompted classes per
     slice."""
     n, S = vol.shape[0], vol.shape[-1]
