@@ -141,6 +141,15 @@ int psam_alp_bank(const float* sup, int ld, int h, int w, int C, const float* ma
  * models/alpmodule.py:57-94 (get_prediction_from_prototypes), :195. which_only -1: both banks. */
 int psam_alp_sim(const float* qry, long long q_bstride, int ld, int B, int npix, int C, const float* bank, int cap,
                  const int* meta, float eps, float sim_scale, float* part, float* pred, int which_only, void* stream);
+/* psam_alp_sim over a table of (query slice, bank) entries in one launch (grid: pixel tiles x 96-prototype groups x entries).
+ * tab: device array of n_entries 32-byte entries {const float* bank; const int* meta; int cap; int b; int flags; int plane;},
+ * flags bit 0 = which (0 bg, 1 fg), bit 1 = direct (the plane's only entry and ceil(cap/96) == 1); entries that feed one output
+ * plane are adjacent. Plane pred + plane*npix gets exactly what psam_alp_sim writes for that slice and bank, and the fmaxf over
+ * its entries in table order when several feed it (the foreground of K shots). max_groups = max ceil(cap/96) over the entries;
+ * part: scratch fp32 [n_entries * max_groups * npix_pad * 3], npix_pad = ceil(npix/64)*64, null when every entry is direct.
+ * models/alpmodule.py:57-94 (get_prediction_from_prototypes), :195; models/grid_proto_fewshot.py:244-266 (shots). */
+int psam_alp_sim_pairs(const float* qry, long long q_bstride, int ld, int npix, int C, const void* tab, int n_entries,
+                       int max_groups, float eps, float sim_scale, float* part, float* pred, void* stream);
 
 /* ---- resampling / packing -------------------------------------------------------------------------------------- */
 /* F.interpolate(img,(S,S),'bilinear') + im2col of a PxP/stride-P conv -> half [B*(S/P)^2, Kpad].

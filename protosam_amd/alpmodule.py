@@ -43,6 +43,12 @@ class MultiProtoAsConv(nn.Module):
         return ops.alp_sim(qry_tok, q_bstride, ld, B, npix, self.embed_dim, bank, pred=pred, eps=safe_norm_eps(),
                            sim_scale=20.0, which_only=which_only)
 
+    def scores_pairs(self, qry_tok, q_bstride, ld, B, npix, banks, entries, n_planes, pred=None):
+        """`scores_token_major` for a table of (bank, slice, which, plane) entries in one launch (ops.plan_alp_pairs) -> fp32
+        [n_planes, npix]; a plane fed by several entries (the shots' foregrounds) holds their element-wise max."""
+        return ops.alp_sim_pairs(qry_tok, q_bstride, ld, B, npix, self.embed_dim, banks, entries, n_planes, pred=pred,
+                                 eps=safe_norm_eps(), sim_scale=20.0)
+
     @staticmethod
     def merge_banks(banks, which):
         """One bank holding the background (which = 0) or foreground (1) prototypes of several banks, concatenated in order: what

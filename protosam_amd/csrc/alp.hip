@@ -338,6 +338,21 @@ __global__ __launch_bounds__(256) void alp_sim_kernel(const float* __restrict__ 
 }
 
 // ---- kernel E: merge proto-tile partials -> pred[b, bank, pix] = sum(softmax(d) * d) --------------------
+// the (max, Z, W) partials of nt prototype groups of one pixel, p + i * gstride for group i, merged in group order -> W / Z
+__device__ __forceinline__ float alp_merge_groups(const float* __restrict__ p, size_t gstride, int nt) {
+  float m = -INFINITY, Z = 0.f, W = 0.f;
+  for (int i = 0; i < nt; ++i, p += gstride) {
+    float mi = p[0];
+    float mm = fmaxf(m, mi);
+    float ea = m > -INFINITY ? expf(m - mm) : 0.f;
+    float eb = mi > -INFINITY ? expf(mi - mm) : 0.f;
+    Z = Z * ea + p[1] * eb;
+    W = W * ea + p[2] * eb;
+    m = mm;
+  }
+  return W / Z;
+}
+
 __global__ void alp_combine_kernel(const float* __restrict__ part, const int* __restrict__ meta, int npt, int npix,
                                    int npix_pad, float* __restrict__ pred, int which_only, int gsize) {
   const int z = blockIdx.y;  // b*2 + bank
@@ -347,18 +362,7 @@ __global__ void alp_combine_kernel(const float* __restrict__ part, const int* __
   const int n = (z & 1) ? meta[META_NFG] : meta[META_NBG];
   // (an empty bank: kernel D2's first group still writes (-inf, 0, 0); kernel D writes nothing; either way pred = 0 / 0)
   const int nt = n > 0 ? (n + gsize - 1) / gsize : (gsize == 96 ? 1 : 0);
-  float m = -INFINITY, Z = 0.f, W = 0.f;
-  for (int i = 0; i < nt && i < npt; ++i) {
-    const float* p = part + (((size_t)z * npt + i) * npix_pad + x) * 3;
-    float mi = p[0];
-    float mm = fmaxf(m, mi);
-    float ea = m > -INFINITY ? expf(m - mm) : 0.f;
-    float eb = mi > -INFINITY ? expf(mi - mm) : 0.f;
-    Z = Z * ea + p[1] * eb;
-    W = W * ea + p[2] * eb;
-    m = mm;
-  }
-  pred[(size_t)z * npix + x] = W / Z;
+  pred[(size_t)z * npix + x] = alp_merge_groups(part + ((size_t)z * npt * npix_pad + x) * 3, (size_t)npix_pad * 3, nt < npt ? nt : npt);
 }
 
 // ---- kernel D2: similarity GEMM + softmax-weighted sum in ONE pass (the default; D + E above are kept for A/B) -------------
@@ -373,23 +377,17 @@ __global__ void alp_combine_kernel(const float* __restrict__ part, const int* __
 // registers. A bank of one group writes pred = W / Z directly; otherwise the per-pixel (max, Z, W) of the group goes to `part`
 // and kernel E merges the groups.
 #define S2_LD 36
-template <int NWV>   // waves per workgroup = 32-pixel strips sharing one prototype group's LDS image
-__global__ __launch_bounds__(NWV * 64) void alp_sim2_kernel(const float* __restrict__ qry, size_t q_bstride, int ld, int npix, int C,
-                                                       const float* __restrict__ bank, int cap, const int* __restrict__ meta,
-                                                       float eps, float sim_scale, float* __restrict__ pred, int which_only, int dbg,
-                                                       float* __restrict__ part, int npt, int npix_pad) {
+// The body of kernel D2, shared by alp_sim2_kernel (one bank) and alp_sim_pairs_kernel (a table of (slice, bank) entries): query
+// pixels [x0, x0 + NWV*32) of Q against prototypes [g0, g0 + 96) of the n rows of P. -> this lane's pixel's (max, Z, W) of the
+// group in (mo_, Zo_, Wo_): lanes 0..31 of wave wv hold pixel x0 + wv*32 + lane (lanes 32..63 the same values).
+template <int NWV>
+__device__ __forceinline__ void alp_sim2_group(const float* __restrict__ Q, int ld, int npix, int C, const float* __restrict__ P,
+                                               int n, int g0, int x0, float eps, float sim_scale, int dbg, float& mo_, float& Zo_,
+                                               float& Wo_) {
   constexpr int PX = NWV * 32, NT = NWV * 64;
   constexpr int QI = PX * 8 / NT, PI = 96 * 8 / NT, RSTEP = NT / 8;   // float4 loads per thread and stage, row step between them
   __shared__ __attribute__((aligned(16))) float Qs[2][PX * S2_LD];
   __shared__ __attribute__((aligned(16))) float Ps[2][96 * S2_LD];
-  const int z = blockIdx.z, b = z >> 1, which = z & 1;
-  if (which_only >= 0 && which != which_only) return;
-  const int n = which ? meta[META_NFG] : meta[META_NBG];
-  const int g0 = blockIdx.y * 96;
-  if (g0 >= n && g0 > 0) return;
-  const int x0 = blockIdx.x * PX;
-  const float* Q = qry + (size_t)b * q_bstride;
-  const float* P = bank + (size_t)(which * cap) * C;
   const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
   const int lr = lane & 31, lk = lane >> 5;
   const int srow = t >> 3, sc4 = (t & 7) * 4;           // staging: rows srow + 16 i, floats sc4 .. sc4 + 3 of the stage
@@ -496,6 +494,27 @@ __global__ __launch_bounds__(NWV * 64) void alp_sim2_kernel(const float* __restr
   const float mm = fmaxf(m, mo);
   const float ea = m > -INFINITY ? expf(m - mm) : 0.f, eb = mo > -INFINITY ? expf(mo - mm) : 0.f;
   const float Zt = Z * ea + Zo * eb, Wt = W * ea + Wo * eb;
+  mo_ = mm;
+  Zo_ = Zt;
+  Wo_ = Wt;
+}
+
+template <int NWV>   // waves per workgroup = 32-pixel strips sharing one prototype group's LDS image
+__global__ __launch_bounds__(NWV * 64) void alp_sim2_kernel(const float* __restrict__ qry, size_t q_bstride, int ld, int npix, int C,
+                                                       const float* __restrict__ bank, int cap, const int* __restrict__ meta,
+                                                       float eps, float sim_scale, float* __restrict__ pred, int which_only, int dbg,
+                                                       float* __restrict__ part, int npt, int npix_pad) {
+  constexpr int PX = NWV * 32;
+  const int z = blockIdx.z, b = z >> 1, which = z & 1;
+  if (which_only >= 0 && which != which_only) return;
+  const int n = which ? meta[META_NFG] : meta[META_NBG];
+  const int g0 = blockIdx.y * 96;
+  if (g0 >= n && g0 > 0) return;
+  const int x0 = blockIdx.x * PX;
+  float mm, Zt, Wt;
+  alp_sim2_group<NWV>(qry + (size_t)b * q_bstride, ld, npix, C, bank + (size_t)(which * cap) * C, n, g0, x0, eps, sim_scale, dbg,
+                      mm, Zt, Wt);
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, lr = lane & 31, lk = lane >> 5;
   const int x = x0 + wv * 32 + lr;
   if (lk == 0 && x < npix) {
     if (npt == 1) {
@@ -507,6 +526,68 @@ __global__ __launch_bounds__(NWV * 64) void alp_sim2_kernel(const float* __restr
       o[2] = Wt;
     }
   }
+}
+
+// ---- kernels D2 and E over a table of (query slice, bank) entries (psam_alp_sim_pairs) -------------------------------------------
+// Every entry runs exactly kernel D2's arithmetic for its slice and bank (alp_sim2_group<4>, the same 96-prototype groups), and every
+// output plane exactly kernel E's merge of its entry's groups; a plane fed by several entries (the foreground of K shots) takes the
+// fmaxf of their results in table order (FewShotSeg._match's torch.maximum chain). Entries of one plane are adjacent in the table.
+struct AlpPairEntry {   // 32 bytes, built on the host (ops.alp_sim_pairs)
+  const float* bank;    // fp32 [2*cap, C], psam_alp_bank's layout
+  const int* meta;      // its counts
+  int cap;
+  int b;                // query slice
+  int flags;            // bit 0: which (0 background, 1 foreground); bit 1: direct - the plane's only entry, one group: write W / Z
+  int plane;            // output plane: pred + plane * npix
+};
+static_assert(sizeof(AlpPairEntry) == 32, "AlpPairEntry is mirrored by ops.alp_sim_pairs");
+
+// dbg is 0, but a kernel argument as in alp_sim2_kernel: with a constant there the compiler schedules and contracts the |q|^2 sums
+// of the shared body differently, and the planes are no longer bit-identical to psam_alp_sim's
+__global__ __launch_bounds__(256) void alp_sim_pairs_kernel(const float* __restrict__ qry, size_t q_bstride, int ld, int npix, int C,
+                                                            const AlpPairEntry* __restrict__ tab, float eps, float sim_scale,
+                                                            float* __restrict__ pred, int dbg, float* __restrict__ part, int ngmax,
+                                                            int npix_pad) {
+  const int e = blockIdx.z;
+  const AlpPairEntry E = tab[e];
+  const int which = E.flags & 1;
+  const int n = which ? E.meta[META_NFG] : E.meta[META_NBG];
+  const int g0 = blockIdx.y * 96;
+  if (g0 >= n && g0 > 0) return;               // (also every group past the entry's own ceil(cap / 96): n <= cap)
+  const int x0 = blockIdx.x * 128;
+  float mm, Zt, Wt;
+  alp_sim2_group<4>(qry + (size_t)E.b * q_bstride, ld, npix, C, E.bank + (size_t)(which * E.cap) * C, n, g0, x0, eps, sim_scale, dbg,
+                    mm, Zt, Wt);
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, lr = lane & 31, lk = lane >> 5;
+  const int x = x0 + wv * 32 + lr;
+  if (lk == 0 && x < npix) {
+    if (E.flags & 2) {
+      pred[(size_t)E.plane * npix + x] = Wt / Zt;
+    } else {
+      float* o = part + (((size_t)e * ngmax + blockIdx.y) * npix_pad + x) * 3;
+      o[0] = mm;
+      o[1] = Zt;
+      o[2] = Wt;
+    }
+  }
+}
+
+// grid.y = entries; the first entry of each plane that is not direct merges the plane
+__global__ void alp_pairs_combine_kernel(const AlpPairEntry* __restrict__ tab, int n_entries, const float* __restrict__ part, int ngmax,
+                                         int npix, int npix_pad, float* __restrict__ pred) {
+  const int e = blockIdx.y;
+  const int plane = tab[e].plane;
+  if ((tab[e].flags & 2) || (e > 0 && tab[e - 1].plane == plane)) return;
+  const int x = blockIdx.x * blockDim.x + threadIdx.x;
+  if (x >= npix) return;
+  float r = 0.f;
+  for (int j = e; j < n_entries && tab[j].plane == plane; ++j) {
+    const int n = (tab[j].flags & 1) ? tab[j].meta[META_NFG] : tab[j].meta[META_NBG];
+    const int ng = (tab[j].cap + 95) / 96, nt = n > 0 ? (n + 95) / 96 : 1;
+    const float v = alp_merge_groups(part + ((size_t)j * ngmax * npix_pad + x) * 3, (size_t)npix_pad * 3, nt < ng ? nt : ng);
+    r = j == e ? v : fmaxf(r, v);
+  }
+  pred[(size_t)plane * npix + x] = r;
 }
 
 // mres: scratch fp32 [2*h*w] (nearest-resized fg mask, then bg mask). bmask may be null (= 1 - mask).
@@ -558,5 +639,23 @@ extern "C" int psam_alp_sim(const float* qry, long long q_bstride, int ld, int B
                      cap, meta, eps, sim_scale, part, npt, npix_pad, which_only);
   hipLaunchKernelGGL(alp_combine_kernel, dim3((npix + 255) / 256, 2 * B), dim3(256), 0, s, part, meta, npt, npix,
                      npix_pad, pred, which_only, 64);
+  return psam_launch_status();
+}
+
+// tab: device AlpPairEntry[n_entries], entries of one plane adjacent; max_groups = max over entries of ceil(cap / 96).
+// part: scratch fp32 [n_entries * max_groups * npix_pad * 3] (npix_pad = ceil(npix/64)*64), null when every entry is direct.
+extern "C" int psam_alp_sim_pairs(const float* qry, long long q_bstride, int ld, int npix, int C, const void* tab, int n_entries,
+                                  int max_groups, float eps, float sim_scale, float* part, float* pred, void* stream) {
+  if (npix <= 0 || (C % 32) != 0 || n_entries <= 0 || n_entries > 65535 || max_groups <= 0 || max_groups > 65535 || !tab || !pred)
+    return PSAM_ERR_ARG;
+  if ((ld % 4) != 0 || (q_bstride % 4) != 0 || (reinterpret_cast<uintptr_t>(qry) & 15) != 0) return PSAM_ERR_ARG;   // float4 loads
+  const int npix_pad = (npix + 63) / 64 * 64;
+  hipStream_t s = (hipStream_t)stream;
+  const AlpPairEntry* t = reinterpret_cast<const AlpPairEntry*>(tab);
+  hipLaunchKernelGGL(alp_sim_pairs_kernel, dim3((npix + 127) / 128, max_groups, n_entries), dim3(256), 0, s, qry, (size_t)q_bstride, ld,
+                     npix, C, t, eps, sim_scale, pred, 0, part, max_groups, npix_pad);
+  if (part)
+    hipLaunchKernelGGL(alp_pairs_combine_kernel, dim3((npix + 255) / 256, n_entries), dim3(256), 0, s, t, n_entries, part, max_groups,
+                       npix, npix_pad, pred);
   return psam_launch_status();
 }

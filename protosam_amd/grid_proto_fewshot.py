@@ -51,6 +51,10 @@ def collapse_lora_state_dict(sd, scale=1.0):
 
 
 class FewShotSeg(nn.Module):
+    # support banks kept by `_support_bank` (and merged background banks by `_merged_bg_bank`): a whole volume's per-class supports,
+    # C classes x 3 z-parts x K shots (`class_scores_supports`)
+    SUPPORT_CACHE = 64
+
     def __init__(self, image_size, pretrained_path=None, cfg=None, cache_support=True):
         super().__init__()
         self.image_size = image_size
@@ -165,19 +169,24 @@ class FewShotSeg(nn.Module):
         if self.cache_support:
             self._sup_cache.insert(0, (supp, fg, bg, (pool_w, getattr(self.encoder, "_weights_epoch", 0)),
                                        (supp._version, fg._version), bank, tok))
-            del self._sup_cache[16:]          # (3 z-parts x a few shots)
+            del self._sup_cache[self.SUPPORT_CACHE:]
         return bank, tok
 
     def _merged_bg_bank(self, banks):
         """n_shots > 1: the background classifier sees every shot's grid prototypes at once, concatenated in shot order
         (grid_proto_fewshot.py:239-240 hands all shots to one `cls_unit` call; alpmodule.py:111-131). Built once per set of shot
-        banks (one 8-int read per shot to size it) and cached beside them."""
+        banks (one 8-int read per shot to size it) and cached beside them, one entry per set of shot banks (an LRU of
+        SUPPORT_CACHE entries: the multi-shot classes of one call must not evict each other)."""
         key = tuple(id(b) for b in banks)
-        hit = self.__dict__.get("_ms_cache")
-        if hit is not None and hit[0] == key:
-            return hit[2]
+        cache = self.__dict__.setdefault("_ms_cache", [])
+        for i, (k, _, merged) in enumerate(cache):
+            if k == key:
+                if i:
+                    cache.insert(0, cache.pop(i))
+                return merged
         merged = self.cls_unit.merge_banks(banks, 0)
-        self._ms_cache = (key, list(banks), merged)      # (holds the shot banks: their ids stay unique while this entry lives)
+        cache.insert(0, (key, list(banks), merged))      # (holds the shot banks: their ids stay unique while this entry lives)
+        del cache[self.SUPPORT_CACHE:]
         return merged
 
     def _shot_banks(self, supp_imgs, fore_mask, back_mask, pool_w):
@@ -265,18 +274,69 @@ class FewShotSeg(nn.Module):
     def class_scores(self, supp_img, fore_masks, qry_imgs, isval=True, val_wsize=None):
         """Several 1-way episodes on the SAME support image (the multi-class loop of /root/reference/validation.py:207, BASELINE
         config 5: one prototype bank per class mask in fore_masks, each [1,H,W]) for B query slices: the support is encoded ONCE,
-        the B queries in ONE encoder forward, and their tokens are matched against every class's bank, each class's scores written
-        straight into one tensor. Returns fp32 [C, B, 2, g, g] (class-major: plane c * B + b of a [C*B, 2, g, g] view is class c of
+        the B queries in ONE encoder forward, and their tokens are matched against every class's bank in ONE psam_alp_sim_pairs
+        launch (`_class_match`), each class's scores written straight into one tensor. Returns fp32 [C, B, 2, g, g] (class-major: plane c * B + b of a [C*B, 2, g, g] view is class c of
         slice b); at B = 1 the bilinear resize of plane c to the image size is the logits `forward(...)` of class c alone."""
-        S, g = self._grid()
         pool_w = val_wsize if (isval and val_wsize is not None) else self.cls_unit.kernel_size[0]
         banks = self._class_banks(supp_img, fore_masks, pool_w)
+        B = qry_imgs.shape[0]
+        return self._class_match(qry_imgs, [[(bank, [bank], B)] for bank in banks])
+
+    @torch.no_grad()
+    def class_scores_supports(self, supports, qry_imgs):
+        """`class_scores` with a support set of its own per class (the reference's per-organ episodes, validation_protosam.py:346-388:
+        each class takes its support slice from its own z-list, ManualAnnoDatasetv2.py:457-477, and a slice's z-part is measured
+        against each class's own extent, common.py:236-249). supports[c] is what `forward_batch` takes as `coarse_model_input` for
+        class c: one ALPNetInput for all B slices, or a list of (ALPNetInput, n) runs in batch order; each input may hold several
+        shots. Every bank is built first (`_shot_banks`: the content-equality LRU), then ONE encoder forward of the B queries and ONE
+        psam_alp_sim_pairs launch. Returns fp32 [C, B, 2, g, g] (class_scores' layout); the bilinear resize of plane (c, b) to the
+        support image size is `forward_groups(qry_imgs, <runs of class c>)[b]`."""
+        B = qry_imgs.shape[0]
+        img_size = None
+        class_runs = []
+        for c, spec in enumerate(supports):
+            runs = list(spec) if isinstance(spec, (list, tuple)) else [(spec, B)]
+            if sum(n for _, n in runs) != B or any(n < 0 for _, n in runs):
+                raise ValueError(f"supports[{c}]: the run counts {[n for _, n in runs]} do not sum to the {B} query slices")
+            cruns = []
+            for inp, n in runs:
+                if len(inp.supp_imgs) != 1:
+                    raise AssertionError("Multi-shot has not been implemented yet")      # (one way per input, as _shot_banks)
+                for shot in inp.supp_imgs[0]:
+                    if img_size is None:
+                        img_size = tuple(shot.shape[-2:])
+                    elif tuple(shot.shape[-2:]) != img_size:
+                        raise ValueError(f"supports[{c}]: support image size {tuple(shot.shape[-2:])} differs from {img_size}; every "
+                                         "support of one call must have the same size (the scores are resized to it)")
+                pool_w = inp.val_wsize if (inp.isval and inp.val_wsize is not None) else self.cls_unit.kernel_size[0]
+                fgs = [bank for bank, _ in self._shot_banks(inp.supp_imgs, inp.fore_mask, inp.back_mask, pool_w)]
+                cruns.append((fgs[0] if len(fgs) == 1 else self._merged_bg_bank(fgs), fgs, n))
+            class_runs.append(cruns)
+        return self._class_match(qry_imgs, class_runs)
+
+    def _class_match(self, qry_imgs, class_runs):
+        """The match under `class_scores` and `class_scores_supports`: class_runs[c] = [(background bank, foreground banks (one per
+        shot), n), ...] in batch order, every bank already built. ONE encoder forward of the queries, ONE psam_alp_sim_pairs launch
+        into [C, B, 2, g, g]: per (class, slice) exactly `_match`'s scores against that run's banks."""
+        S, g = self._grid()
+        banks, index = [], {}
+
+        def slot(bank):
+            k = index.get(id(bank))
+            if k is None:
+                k = index[id(bank)] = len(banks)
+                banks.append(bank)
+            return k
+        runs = []
+        for cr in class_runs:
+            runs.append([(slot(bg), [slot(f) for f in fgs], n) for bg, fgs, n in cr])
+            for bg, _, _ in cr:
+                self._check_bank(bg)
+        B = qry_imgs.shape[0]
+        entries, n_planes = ops.plan_alp_pairs(runs, B)
         qry_tok, q_bstride, q_ld = self._patch_tokens(qry_imgs)
-        B = qry_tok.shape[0]
-        out = torch.empty((len(banks), B, 2, g, g), dtype=torch.float32, device=qry_imgs.device)
-        for c, bank in enumerate(banks):
-            self.cls_unit.scores_token_major(qry_tok, q_bstride, q_ld, B, g * g, bank, pred=out[c].view(B, 2, g * g))
-            self._check_bank(bank)
+        out = torch.empty((len(class_runs), B, 2, g, g), dtype=torch.float32, device=qry_imgs.device)
+        self.cls_unit.scores_pairs(qry_tok, q_bstride, q_ld, B, g * g, banks, entries, n_planes, pred=out.view(n_planes, g * g))
         return out
 
     def _class_banks(self, supp_img, fore_masks, pool_w):

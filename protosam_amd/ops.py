@@ -554,6 +554,74 @@ def alp_sim(qry, q_bstride, ld, B, npix, C, bank, pred=None, part=None, eps=1e-4
     return pred
 
 
+def plan_alp_pairs(class_runs, B):
+    """The entry list of `alp_sim_pairs` for C classes x B query slices (pure Python). class_runs[c]: the runs of class c in batch
+    order, each (bg, fgs, n): the next n slices are matched against background bank `bg` and foreground banks `fgs` (one per shot;
+    bg is the shots' merged bank when there are several). Banks are whatever handles the caller uses (indices into its bank list).
+    Output planes follow FewShotSeg.class_scores' class-major layout [C, B, 2, ...]: plane (c*B + b)*2 + which. -> (entries, n_planes),
+    entries = [(bank, b, which, plane), ...] ordered by plane, a plane's shots adjacent in shot order."""
+    entries = []
+    for c, runs in enumerate(class_runs):
+        if sum(n for _, _, n in runs) != B or any(n < 0 for _, _, n in runs):
+            raise ValueError(f"class {c}: the run counts {[n for _, _, n in runs]} do not sum to the {B} query slices")
+        b0 = 0
+        for bg, fgs, n in runs:
+            if not fgs:
+                raise ValueError(f"class {c}: a run without a foreground bank")
+            for b in range(b0, b0 + n):
+                plane = (c * B + b) * 2
+                entries.append((bg, b, 0, plane))
+                entries.extend((f, b, 1, plane + 1) for f in fgs)
+            b0 += n
+    return entries, 2 * B * len(class_runs)
+
+
+def alp_sim_pairs(qry, q_bstride, ld, B, npix, C, banks, entries, n_planes, pred=None, part=None, eps=1e-4, sim_scale=20.0):
+    """qry fp32 token-major [B][npix, C]; banks: AlpBank list; entries: [(bank index, slice b, which, plane), ...] (`plan_alp_pairs`)
+    -> pred fp32 [n_planes, npix]: plane p = psam_alp_sim's (slice b, which) plane for the entry's bank, the element-wise max over
+    the entries when several feed p (in their order). One small host-to-device copy of the entry table, one psam_alp_sim_pairs."""
+    _req(qry, torch.float32, "qry")
+    if not entries:
+        raise ValueError("alp_sim_pairs: no entries")
+    count = {}
+    last = None
+    for i, (k, b, which, plane) in enumerate(entries):
+        if not (0 <= k < len(banks) and 0 <= b < B and which in (0, 1) and 0 <= plane < n_planes):
+            raise ValueError(f"alp_sim_pairs: entry {i} {(k, b, which, plane)} is out of range")
+        if plane != last and plane in count:
+            raise ValueError(f"alp_sim_pairs: the entries of plane {plane} are not adjacent")
+        count[plane] = count.get(plane, 0) + 1
+        last = plane
+    for bk in banks:
+        if bk.C != C or bk.bank.device != qry.device:
+            raise ValueError("alp_sim_pairs: every bank must have the query's channel count and device")
+    rows, ngmax, direct = [], 1, True
+    for k, b, which, plane in entries:
+        bk = banks[k]
+        ng = (bk.cap + 95) // 96
+        ngmax = max(ngmax, ng)
+        d = count[plane] == 1 and ng == 1
+        direct = direct and d
+        rows.append([bk.bank.data_ptr(), bk.meta.data_ptr(), bk.cap | (b << 32), (which | (2 if d else 0)) | (plane << 32)])
+    npix_pad = (npix + 63) // 64 * 64
+    if part is None and not direct:
+        part = torch.empty(len(entries) * ngmax * npix_pad * 3, dtype=torch.float32, device=qry.device)
+    assert part is None or part.numel() >= len(entries) * ngmax * npix_pad * 3
+    if pred is None:
+        pred = torch.empty((n_planes, npix), dtype=torch.float32, device=qry.device)
+    _req(pred, torch.float32, "pred")
+    assert pred.is_contiguous() and pred.numel() >= n_planes * npix
+    # (a pinned staging tensor: the caching host allocator keeps it until the copy has run)
+    tab = torch.tensor(rows, dtype=torch.int64).pin_memory().to(qry.device, non_blocking=True)
+    h = _tstart("alp_sim")
+    st = _lib.lib().psam_alp_sim_pairs(_ptr(qry), q_bstride, ld, npix, C, _ptr(tab), len(entries), ngmax, float(eps), float(sim_scale),
+                                       _ptr(part), _ptr(pred), _stream())
+    _tstop(h, (B * npix * C * 4 + sum(2 * bk.cap * C * 4 for bk in banks) + n_planes * npix * 4,
+               sum(2.0 * npix * C * banks[k].cap for k, _, _, _ in entries)))
+    _lib.check(st, "psam_alp_sim_pairs")
+    return pred
+
+
 # ---- resampling / packing ---------------------------------------------------------------------------------
 def patchify_bilinear(img, S, P, Kpad, out=None):
     _req(img, torch.float32, "img")

@@ -18,7 +18,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .protosam import DECODER_CHUNK, MAX_COMPONENTS, ModelWrapper, ProtoSAM
+from .protosam import DECODER_CHUNK, MAX_COMPONENTS, ModelWrapper, ProtoSAM, class_support_scores
 from .segment_anything import sam_model_registry
 
 CCL_SLOTS = 32   # planes per connected-components launch chain of the batched paths (~8 MB of CCL scratch per slot at 1024^2)
@@ -320,7 +320,7 @@ class ProtoMedSAM(nn.Module):
         return [r[0] for r in results]
 
     @torch.no_grad()
-    def forward_classes_batch(self, query_images, support_image, support_masks, val_wsize=2, out=None):
+    def forward_classes_batch(self, query_images, support_image=None, support_masks=None, val_wsize=2, out=None, supports=None):
         """The config-5 throughput path: B query slices [B,3,H,W] x C classes (support_masks: C masks of `support_image`) in one
         call. Returns results[b][c] = (mask, [conf]), equal to `forward_classes(query_images[b:b+1], ...)[c]`: the masks of the
         classes with a component are views of one uint8 [B,C,H,W] tensor (`out` if given), the others int64 zeros and [0] (that
@@ -331,15 +331,21 @@ class ProtoMedSAM(nn.Module):
         decoder call over every (slice, class) box (chunked by DECODER_CHUNK), ONE psam_mask_union_seg into [B,C,H,W].
         Extra device memory at B = 32, C = 4, 1024^2: 640 MiB of per-plane maps (uint8 arg-max + fp32 softmax(softmax)), ~260 MiB of
         CCL scratch (32 slots), 128 MiB of output masks, 128 MiB of low-res decoder masks, plus the encoder's 32-slice workspace
-        and the decoder's per-prompt workspace (measured peak: see DESIGN.md section 6)."""
+        and the decoder's per-prompt workspace (measured peak: see DESIGN.md section 6).
+        `supports=` (instead of support_image / support_masks): one support spec per class - one ALPNetInput or a list of
+        (ALPNetInput, n) runs in batch order, any number of shots (`ProtoSAM.forward_classes_batch`) - and then results[b][c] is
+        what `forward_batch(query_images, supports[c])[b]` gives."""
         if not self.use_cca or self.coarse_pred_only:
             raise NotImplementedError("forward_classes_batch: use_cca=True, coarse_pred_only=False")
         alp = self.coarse_segmentation_model.model
-        sc = alp.class_scores(support_image, support_masks, query_images, isval=True, val_wsize=val_wsize)   # [C,B,2,g,g]
+        if supports is not None:
+            sc, img_size = class_support_scores(alp, supports, support_image, support_masks, query_images)
+        else:
+            sc = alp.class_scores(support_image, support_masks, query_images, isval=True, val_wsize=val_wsize)   # [C,B,2,g,g]
+            img_size = tuple(support_image.shape[-2:])
         C, B, g = sc.shape[0], sc.shape[1], sc.shape[-1]
         S = self.medsam.image_encoder.img_size
         sc = sc.view(C * B, 2, g, g)
-        img_size = tuple(support_image.shape[-2:])
         if img_size != (S, S):     # the coarse logits live at the image size (FewShotSeg.forward): resized there first, then to 1024
             sc = ops.bilinear_nchw(sc, img_size[0], img_size[1])
         results, _, self.last_stats = self._segment(query_images, sc, C, relabel=False, out=out)

@@ -111,6 +111,20 @@ class StageTimer:
 STAGE_TIMER = None
 
 
+def class_support_scores(alp, supports, support_image, support_masks, query_images):
+    """The `supports=` form of both forward_classes_batch methods: one support spec per class (see ProtoSAM.forward_classes_batch)
+    -> (coarse scores [C,B,2,g,g] from FewShotSeg.class_scores_supports, the support image size the scores are resized to)."""
+    if support_image is not None or support_masks is not None:
+        raise TypeError("forward_classes_batch: pass either supports= or support_image / support_masks, not both")
+    if not isinstance(supports, (list, tuple)) or not supports:
+        raise ValueError("forward_classes_batch: supports= takes a non-empty list with one support spec per class")
+    if not hasattr(alp, "class_scores_supports"):
+        raise TypeError("forward_classes_batch(supports=) needs a coarse model with class_scores_supports (ALPNetWrapper(FewShotSeg))")
+    sc = alp.class_scores_supports(supports, query_images)           # [C,B,2,g,g]; checks that every support has one size
+    first = supports[0][0][0] if isinstance(supports[0], (list, tuple)) else supports[0]
+    return sc, tuple(first.supp_imgs[0][0].shape[-2:])
+
+
 def _mark(name):
     if STAGE_TIMER is not None:
         STAGE_TIMER.mark(name)
@@ -817,7 +831,8 @@ class ProtoSAM(nn.Module):
         return c, l
 
     @torch.no_grad()
-    def forward_classes_batch(self, query_images, support_image, support_masks, val_wsize=2, out=None, degrees_rotate=0):
+    def forward_classes_batch(self, query_images, support_image=None, support_masks=None, val_wsize=2, out=None, degrees_rotate=0,
+                              supports=None):
         """The multi-class path (validation_protosam.py runs one 1-way episode per organ on the same slices): B query slices
         [B,3,H,W] x C classes (support_masks: C masks of ONE support image) in one call. Returns results[b][c] = (mask, scores),
         what `forward(query_images[b:b+1], ALPNetInput(support_image, [support_masks[c]], ...))` gives: the masks are uint8 views
@@ -828,11 +843,34 @@ class ProtoSAM(nn.Module):
         table taken before the next chunk overwrites its labels -> ONE SAM encoder forward of the slices where some class has
         foreground -> the prompt sets of every (slice, class) -> the batched decoder -> ONE psam_mask_union_seg into [B,C,H,W].
         `last_stats`: prompt / spans ((b, c) -> rows of low_res), prompts ((b, c) -> its prompt sets), n_prompted, n_encoded,
-        n_components [B][C], low_res, iou, sel."""
+        n_components [B][C], low_res, iou, sel.
+        `supports=` (instead of support_image / support_masks): one support spec per class, what `forward_batch` takes as
+        `coarse_model_input` - one ALPNetInput, or a list of (ALPNetInput, n) runs in batch order, each with one or more shots - so
+        that every class has its own support slice per z-part (the reference's per-organ episodes). Then results[b][c] is what
+        `forward_batch(query_images, supports[c])[b]` gives; only the prototype match differs (FewShotSeg.class_scores_supports)."""
         if self.training:
             raise NotImplementedError("training-mode outputs (logits) are outside the inference hot path")
         if degrees_rotate != 0:
             raise NotImplementedError("forward_classes_batch: rotation TTA (degrees_rotate != 0); use forward_batch per class")
+        alp = getattr(self.coarse_segmentation_model, "model", None)
+        if supports is not None:
+            sc, (IH, IW) = class_support_scores(alp, supports, support_image, support_masks, query_images)
+        else:
+            sc, (IH, IW) = self._shared_support_scores(alp, query_images, support_image, support_masks, val_wsize)
+        C, B, gh, gw = sc.shape[0], sc.shape[1], sc.shape[-2], sc.shape[-1]
+        P = C * B
+        sc = sc.view(P, 2, gh, gw)
+        H = query_images.shape[-2]
+        dev = query_images.device
+        if self.coarse_pred_only:                       # ProtoSAM.py:580-590 per plane
+            res = self._coarse_only_batch(ops.bilinear_nchw(sc.contiguous(), IH, IW), H)
+            self.last_stats = dict(n_slices=B, n_classes=C)
+            return [[res[c * B + b] for c in range(C)] for b in range(B)]
+        return self._classes_segment(query_images, sc, C, B, IH, IW, out)
+
+    @staticmethod
+    def _shared_support_scores(alp, query_images, support_image, support_masks, val_wsize):
+        """forward_classes_batch's original form: C masks of one support image -> (scores [C,B,2,g,g], support image size)"""
         if isinstance(support_image, (list, tuple)):
             if any(isinstance(x, (list, tuple)) for x in support_image):
                 raise NotImplementedError("forward_classes_batch: one support image per call (mixed supports); call once per support")
@@ -843,20 +881,16 @@ class ProtoSAM(nn.Module):
             raise NotImplementedError("forward_classes_batch: one support shot [1,3,H,W] (multi-shot support)")
         if any(isinstance(m, (list, tuple)) for m in support_masks):
             raise NotImplementedError("forward_classes_batch: one support mask per class (multi-shot support)")
-        alp = getattr(self.coarse_segmentation_model, "model", None)
         if not hasattr(alp, "class_scores"):
             raise TypeError("forward_classes_batch needs a coarse model with class_scores (ALPNetWrapper(FewShotSeg))")
         sc = alp.class_scores(support_image, support_masks, query_images, isval=True, val_wsize=val_wsize)   # [C,B,2,g,g]
-        C, B, gh, gw = sc.shape[0], sc.shape[1], sc.shape[-2], sc.shape[-1]
+        return sc, tuple(support_image.shape[-2:])    # (the image size FewShotSeg.forward resizes its logits to)
+
+    def _classes_segment(self, query_images, sc, C, B, IH, IW, out):
+        """forward_classes_batch after the coarse scores sc [P,2,g,g] (plane c*B + b), whatever support form produced them"""
         P = C * B
-        sc = sc.view(P, 2, gh, gw)
-        IH, IW = support_image.shape[-2:]              # the image size FewShotSeg.forward resizes its logits to
         H = query_images.shape[-2]
         dev = query_images.device
-        if self.coarse_pred_only:                       # ProtoSAM.py:580-590 per plane
-            res = self._coarse_only_batch(ops.bilinear_nchw(sc.contiguous(), IH, IW), H)
-            self.last_stats = dict(n_slices=B, n_classes=C)
-            return [[res[c * B + b] for c in range(C)] for b in range(B)]
         sam = self.sam
         S = sam.image_encoder.img_size
         cb = self._class_bufs(dev, P, B)

@@ -6,6 +6,7 @@ data-path collective; the only exchange is one all-gather of the uint8 masks per
 """
 import math
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
@@ -134,6 +135,97 @@ def run_slices_classes(model, vol, sup_imgs, sup_masks_per_part, zs, device, bat
         for (k, _) in model.last_stats.get("prompt", {}):          # (slice, class) pairs that went to the decoder
             stats[i + k] += 1
         i = j
+    return out, stats
+
+
+def _class_zlists(label_vol, classes):
+    """per class: the sorted z indices of label_vol [Z,H,W] (tensor or array of integer labels) where the class has a pixel (the
+    reference's per-scan `tp1_cls_map` lists); ValueError for a class the scan does not hold"""
+    lab = label_vol.detach().cpu().numpy() if isinstance(label_vol, torch.Tensor) else np.asarray(label_vol)
+    out = []
+    for c in classes:
+        zl = np.nonzero((lab == c).reshape(lab.shape[0], -1).any(axis=1))[0].tolist()
+        if not zl:
+            raise ValueError(f"class {c} is absent from the scan (the reference's min() of its empty z-list fails)")
+        out.append(zl)
+    return out
+
+
+def class_part_table(label_vol, classes, n_parts=3):
+    """The z-part of every query slice per class -> int64 [C, Z] (dataloaders/common.py:236-249): slice z belongs to part
+    int((z - z_min) // ((z_max - z_min) / n_parts)) of class c, with z_min / z_max the class's own extent in this scan (float floor
+    division), part 0 where z_max == z_min (the reference's `except`), clipped to [0, n_parts - 1]. The same slice can be in
+    different parts for different classes."""
+    zls = _class_zlists(label_vol, classes)
+    Z = label_vol.shape[0]
+    tab = np.zeros((len(classes), Z), dtype=np.int64)
+    for c, zl in enumerate(zls):
+        z_min, z_max = min(zl), max(zl)
+        for z in range(Z):
+            try:
+                part = int((z - z_min) // ((z_max - z_min) / n_parts))
+            except ZeroDivisionError:
+                part = 0
+            tab[c, z] = min(max(part, 0), n_parts - 1)
+    return tab
+
+
+def class_support_slices(sup_label_vol, classes, n_parts=3):
+    """The support slice of every (class, part) -> [C][n_parts] z indices of the support scan (ManualAnnoDatasetv2.py:457-477): part p
+    of class c takes zlist[int(pcts[p] * len(zlist))] of the class's own z-list, pcts = [0.5] for one part, else the centres
+    1/(2 n) + p (1 - 1/n) / (n - 1). n_parts must be odd, as the reference asserts."""
+    if n_parts % 2 != 1:
+        raise ValueError(f"n_parts must be odd (the reference asserts npart % 2 == 1), got {n_parts}")
+    if n_parts == 1:
+        pcts = [0.5]
+    else:
+        half_part = 1 / (n_parts * 2)
+        part_interval = (1.0 - 1.0 / n_parts) / (n_parts - 1)
+        pcts = [half_part + part_interval * ii for ii in range(n_parts)]
+    return [[zl[int(pcts[p] * len(zl))] for p in range(n_parts)] for zl in _class_zlists(sup_label_vol, classes)]
+
+
+def class_support_specs(supports, part_table, zs):
+    """The `supports=` argument of forward_classes_batch for the slices zs of one batch: per class c, supports[c][p] of the part p of
+    every slice (part_table[c][z]), as one input when the batch lies in one part, else as (input, n) runs of equal part."""
+    specs = []
+    for c in range(len(supports)):
+        runs = []                                   # consecutive slices of one part of class c
+        for z in zs:
+            p = int(part_table[c][z])
+            if runs and runs[-1][0] == p:
+                runs[-1][1] += 1
+            else:
+                runs.append([p, 1])
+        specs.append(supports[c][runs[0][0]] if len(runs) == 1 else [(supports[c][p], n) for p, n in runs])
+    return specs
+
+
+@torch.no_grad()
+def run_slices_class_supports(model, vol, supports, part_table, zs, batch=16, out=None):
+    """`run_slices_classes` as the reference evaluates (one 1-way episode per organ): class c has a support input of its own per
+    z-part, supports[c][p] (an ALPNetInput, one or more shots), and slice z is matched against supports[c][part_table[c][z]]
+    (`class_part_table`). `batch` consecutive slices go to one `model.forward_classes_batch(..., supports=...)` call whatever
+    their parts: each class's runs of equal part become its (input, n) list.
+    Returns uint8 masks [len(zs), C, S, S] and the number of prompted classes per slice, as `run_slices_classes`."""
+    S, dev = vol.shape[-1], vol.device
+    C = len(supports)
+    if out is None:
+        out = torch.zeros((len(zs), C, S, S), dtype=torch.uint8, device=dev)
+    stats = [0] * len(zs)
+    for i in range(0, len(zs), batch):
+        zb = list(zs[i:i + batch])
+        idx = torch.tensor(zb, device=dev)
+        q = vol[idx][:, None].expand(len(zb), 3, S, S).contiguous()
+        specs = class_support_specs(supports, part_table, zb)
+        dst = out[i:i + len(zb)]
+        res = model.forward_classes_batch(q, supports=specs, out=dst)
+        for k, per_class in enumerate(res):
+            for c, (mask, _) in enumerate(per_class):
+                if mask.data_ptr() != dst[k, c].data_ptr():        # (an empty class: int64 zeros, and zeros in `dst` already)
+                    dst[k, c].copy_(mask)
+        for (k, _) in model.last_stats.get("prompt", {}):          # (slice, class) pairs that went to the decoder
+            stats[i + k] += 1
     return out, stats
 
 
