@@ -59,8 +59,9 @@ int psam_ln_finalize(const float* stats, int M, int D, float eps, float* mr, voi
  *   x[M,N] (fp32, in place) += A[M,K] . W[N,K]^T + bias;  out16 (optional half [M, ld16]) = LayerNorm(x; ln_w, ln_b, eps), or half(x) when
  *   ln_w is null.
  * `ks` K ranges per tile (ks * tiles workgroups side by side); ws: CALLER-OWNED fp32 scratch of >= ks * Mp * N elements, Mp = M rounded up
- * to a multiple of 256 (the library keeps no
- * state for this path: it may be captured into a graph); the ranges are summed in a fixed order (deterministic).
+ * to a multiple of 256; the ranges are summed in a fixed order (deterministic). The first call per (M, N, ks) on a device builds the
+ * work list of the launch in device memory (hipMalloc + a synchronous hipMemcpy), so it must run OUTSIDE stream capture; later calls of
+ * that shape allocate nothing and may be captured into a graph (the Python path runs every call once eagerly before it captures).
  * psam_gemm_splitk_ranges returns the ks this device would use for the shape (0: the shape does not pay, or the assembly kernel is not
  * loaded) - a count, not a status; psam_gemm_f16_splitk_ln takes exactly that ks (>= 2), N % 256 == 0, N <= 2048, K % 64 == 0.
  * modeling/common.py:13-26 (MLPBlock.lin2) + image_encoder.py:174-193 (x = x + mlp(...), then the next block's norm1). */

@@ -224,6 +224,27 @@ def check_sam_encoder(gold):
     gold["sam_encoder_small_out"] = r.numpy().astype(np.float32)
 
 
+def check_sam_encoder_vit_l():
+    """The oracle's VIT_CFGS["vit_l"] against the reference's ImageEncoderViT built with build_sam_vit_l's hyperparameters (build_sam.py:
+    27-34, _build_sam's fixed arguments) on seeded weights, truncated to 6 blocks: five windowed blocks and the global block 5."""
+    from functools import partial
+    from segment_anything.modeling import ImageEncoderViT  # vendored reference
+    from oracle import sam_image_encoder as oenc
+    from protosam_amd.synth import synth_state_dict
+    depth = 6
+    print(f"SAM ImageEncoderViT, ViT-L hyperparameters (dim 1024, 16 heads, global blocks 5 / 11 / 17 / 23), {depth} blocks")
+    ref = ImageEncoderViT(depth=depth, embed_dim=1024, img_size=1024, mlp_ratio=4, norm_layer=partial(torch.nn.LayerNorm, eps=1e-6),
+                          num_heads=16, patch_size=16, qkv_bias=True, use_rel_pos=True, global_attn_indexes=[5, 11, 17, 23],
+                          window_size=14, out_chans=256).eval()
+    sd = synth_state_dict(ref, 1234)
+    ref.load_state_dict(sd)
+    x = torch.randn((1, 3, 1024, 1024), generator=torch.Generator().manual_seed(3))
+    with torch.no_grad():
+        r = ref(x)
+    o = oenc.image_encoder(x, sd, pre="", model_type="vit_l", depth=depth)
+    close(o, r, 2e-5, f"ViT-L image embedding [1,256,64,64], {depth} blocks")
+
+
 def check_sam_decoder(gold):
     from segment_anything import sam_model_registry  # vendored
     from segment_anything.modeling import Sam
@@ -750,6 +771,7 @@ def main():
     check_fewshot(gold)
     check_dinov2_vs_transformers()
     check_sam_encoder(gold)
+    check_sam_encoder_vit_l()
     check_sam_decoder(gold)
     check_glue(gold)
     check_amg(gold)

@@ -1401,7 +1401,10 @@ static const AsmTable* asm_table(int ntm, int ntn, int mode, int halves = 0, int
   t.grid = G;
   t.dev = nullptr;
   if (hipMalloc((void**)&t.dev, h.size() * sizeof(int)) != hipSuccess) return nullptr;
-  if (hipMemcpy(t.dev, h.data(), h.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) return nullptr;
+  if (hipMemcpy(t.dev, h.data(), h.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) {
+    (void)hipFree(t.dev);                                   // (nothing is cached: a retry allocates again)
+    return nullptr;
+  }
   return &(g_asm_tabs[key] = t);
 }
 // lnf: 0 plain, 1 a folded-LayerNorm launch (tile 15 has _ln forms of its kernels, tile 16 none)
@@ -1523,7 +1526,10 @@ static const AsmTable* asm_table_splitk(int ntm, int ntn, int ks) {
   t.grid = G;
   t.dev = nullptr;
   if (hipMalloc((void**)&t.dev, h.size() * sizeof(int)) != hipSuccess) return nullptr;
-  if (hipMemcpy(t.dev, h.data(), h.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) return nullptr;
+  if (hipMemcpy(t.dev, h.data(), h.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) {
+    (void)hipFree(t.dev);                                   // (nothing is cached: a retry allocates again)
+    return nullptr;
+  }
   return &(g_asm_tabs[key] = t);
 }
 
@@ -1612,7 +1618,8 @@ extern "C" int psam_gemm_splitk_ranges(int M, int N, int K) {
 // x[M,N] (fp32, in place) += A[M,K] . W[N,K]^T + bias; out16 (optional, fp16 [M, ld16]) = LayerNorm(x; ln_w, ln_b, eps), or fp16(x) when
 // ln_w is null. ws: caller-owned fp32 scratch of at least ks * Mp * N elements, Mp = M rounded up to a multiple of 256 (ks =
 // psam_gemm_splitk_ranges(M, N, K), which must be >= 2).
-// Deterministic; touches no library-owned state, so it may be captured into a graph.
+// Deterministic. The first call per (M, N, ks) on a device builds the work list (asm_table_splitk: hipMalloc + hipMemcpy), so it must run
+// outside stream capture; later calls of the shape touch no library-owned state and may be captured into a graph.
 extern "C" int psam_gemm_f16_splitk_ln(const void* A, const void* W, const float* bias, float* x, int M, int N, int K, int lda, int ldw,
                                        int ldx, int ks, float* ws, const float* ln_w, const float* ln_b, float eps, void* out16, int ld16,
                                        void* stream) {

@@ -279,7 +279,9 @@ class ImageEncoderViT(nn.Module):
             big = max((b for b in self._ws if b > B), default=None)
             if big is not None:   # a sub-batch (e.g. only the slices with a non-empty coarse mask): views of the larger set
                 N = self.grid * self.grid
-                self._ws[B] = {k: (v[:6 * B * N] if k == "mr" else v[:B] if v.shape[0] == big else v[:B * N]) for k, v in self._ws[big].items()}
+                # (the 1-D split-K scratch is sized by ks, which differs between batch sizes: each B gets its own, see _splitk_buffer)
+                self._ws[B] = {k: (v[:6 * B * N] if k == "mr" else v[:B] if v.shape[0] == big else v[:B * N]) for k, v in self._ws[big].items()
+                               if k != "sk_ws"}
                 return self._ws[B]
             D, oc, N, H = self.embed_dim, self.out_chans, self.grid * self.grid, self.num_heads
             dev = self.pos_embed.device
@@ -313,6 +315,14 @@ class ImageEncoderViT(nn.Module):
             ws["relh"] = torch.empty((B, H, N, 64), dtype=torch.float32, device=dev)
             ws["relw"] = torch.empty((B, H, N, 64), dtype=torch.float32, device=dev)
         return ws["relh"], ws["relw"]
+
+    def _splitk_buffer(self, ws, sk, M):
+        """fp32 scratch of `ops.gemm_splitk_ln` for mlp.lin2 at M rows in `sk` K ranges: allocated when that path first runs, and again when
+        the one held is smaller than this call needs (ks depends on M: ViT-L takes 4 ranges for one image and 2 for two)."""
+        need = sk * ops.splitk_rows(M) * self.embed_dim
+        if "sk_ws" not in ws or ws["sk_ws"].numel() < need:
+            ws["sk_ws"] = torch.empty(need, dtype=torch.float32, device=self.pos_embed.device)
+        return ws["sk_ws"]
 
     def _pack_x3(self, pk):
         """(hi, lo, scale) splits of the blocks' four Linear weights for ops.gemm_f32x3 (one-time, only when `gemm_x3` runs)."""
@@ -390,8 +400,8 @@ class ImageEncoderViT(nn.Module):
             self._encode_blocks_x3(pk, ws, B)
         # split-K form of mlp.lin2 (see __init__): only without the fold (one or two images), only where the library says it pays
         sk = ops.gemm_splitk_ranges(M, D, 4 * D) if (self.splitk_lin2 and not fold and not x3 and not ops.QKV_HEAD_MAJOR) else 0
-        if sk >= 2 and "sk_ws" not in ws:
-            ws["sk_ws"] = torch.empty(sk * ops.splitk_rows(M) * D, dtype=torch.float32, device=x.device)
+        if sk >= 2:
+            self._splitk_buffer(ws, sk, M)
         ln1_ready = False                                   # ws["ln"] already holds norm1(x) of the block about to run
         nblk = len(pk["blocks"])
         for bi, (blk, bp) in enumerate(zip(self.blocks if not x3 else (), pk["blocks"])):

@@ -105,3 +105,53 @@ def test_t2i_split_mode_one_means_one_range(monkeypatch):
     assert ops.t2i_split(1, 8, 7, 4096) == 4
     monkeypatch.setenv("PSAM_T2I_SPLIT", "auto")
     assert ops.t2i_split(1, 8, 7, 4096) == 16 and ops.t2i_split(27, 8, 7, 4096) == 1
+
+
+def test_vit_l_state_dict_and_oracle_config():
+    """sam_model_registry["vit_l"] (build_sam.py:27-34): D = 1024, 16 heads of 64, 24 blocks, global attention in blocks 5 / 11 / 17 / 23
+    with 127-row rel-pos tables (the 64 x 64 map), 27-row ones in the 14 x 14 windows of every other block; the oracle's VIT_CFGS["vit_l"]
+    describes the same module tree."""
+    from oracle.sam_image_encoder import VIT_CFGS, WINDOW
+    from protosam_amd.segment_anything import sam_model_registry
+    sam = sam_model_registry["vit_l"]()
+    enc = sam.image_encoder
+    sd = sam.state_dict()
+    D, hd = 1024, 64
+    assert enc.embed_dim == D and enc.num_heads == 16 and len(enc.blocks) == 24
+    assert sd["image_encoder.patch_embed.proj.weight"].shape == (D, 3, 16, 16)
+    assert sd["image_encoder.pos_embed"].shape == (1, 64, 64, D)
+    for i in range(24):
+        p = f"image_encoder.blocks.{i}."
+        assert sd[p + "attn.qkv.weight"].shape == (3 * D, D) and sd[p + "attn.qkv.bias"].shape == (3 * D,)
+        assert sd[p + "attn.proj.weight"].shape == (D, D)
+        assert sd[p + "mlp.lin1.weight"].shape == (4 * D, D) and sd[p + "mlp.lin2.weight"].shape == (D, 4 * D)
+        L = 127 if i in (5, 11, 17, 23) else 2 * WINDOW - 1
+        assert sd[p + "attn.rel_pos_h"].shape == (L, hd) and sd[p + "attn.rel_pos_w"].shape == (L, hd), i
+        assert enc.blocks[i].window_size == (0 if L == 127 else WINDOW)
+    assert "image_encoder.blocks.24.norm1.weight" not in sd
+    assert sd["image_encoder.neck.0.weight"].shape == (256, D, 1, 1) and sd["image_encoder.neck.2.weight"].shape == (256, 256, 3, 3)
+    cfg = VIT_CFGS["vit_l"]
+    assert cfg["embed_dim"] == enc.embed_dim and cfg["num_heads"] == enc.num_heads and cfg["depth"] == len(enc.blocks)
+    assert tuple(cfg["global_attn_indexes"]) == tuple(i for i, b in enumerate(enc.blocks) if b.window_size == 0)
+
+
+def test_vit_l_splitk_workspace_follows_the_batch_size():
+    """The split-K scratch of mlp.lin2 (`splitk_lin2`) is sized by the ks of the call, and ViT-L takes 2 ranges for two images but 4 for one
+    (psam_gemm_splitk_ranges on 256 CUs). A one-image workspace built as views of the two-image one must not inherit a truncated scratch:
+    after the B = 2 buffer, the B = 1 call needs 4 x 4096 x 1024 elements of its own, and the B = 2 buffer keeps its size."""
+    from protosam_amd import ops
+    from protosam_amd.segment_anything import sam_model_registry
+    enc = sam_model_registry["vit_l"](encoder_depth=1).image_encoder
+    N, D = 4096, 1024
+    ws2 = enc._workspace(2)
+    b2 = enc._splitk_buffer(ws2, 2, 2 * N)
+    assert b2.numel() >= 2 * ops.splitk_rows(2 * N) * D
+    ws1 = enc._workspace(1)
+    assert ws1["x"].data_ptr() == ws2["x"].data_ptr() and ws1["x"].shape == (N, D)      # (a sub-batch: views of the larger set)
+    b1 = enc._splitk_buffer(ws1, 4, N)
+    assert b1.numel() >= 4 * 4096 * 1024 and ws1["sk_ws"].numel() >= 4 * 4096 * 1024
+    assert enc._workspace(2)["sk_ws"].numel() >= 2 * 8192 * 1024
+    assert enc._splitk_buffer(ws2, 2, 2 * N) is b2 and enc._splitk_buffer(ws1, 4, N) is b1    # (sized once: a captured graph keeps its address)
+    # a buffer that is large enough is kept; a smaller one is replaced
+    ws3 = {"sk_ws": torch.empty(10)}
+    assert enc._splitk_buffer(ws3, 2, N).numel() == 2 * N * D

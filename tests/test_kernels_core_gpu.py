@@ -172,6 +172,100 @@ def test_gemm_half_tile_pingpong(dev, M, N, K, epi):
         assert (outs[0].float() - outs[1].float()).abs().max().item() <= 2 ** -7   # one fp16 ulp at |x| < 16
 
 
+# SAM ViT-L's Linear layers (D = 1024) with the epilogue the encoder runs them with: (N, K, epilogue, residual)
+#   "resid" = x += a w^T + b in place (proj, mlp.lin2); "pos" = the patch embedding's position table (resid_mod = 4096, out of place)
+VIT_L_LINEARS = {"qkv": (3072, 1024, "f16", None), "proj": (1024, 1024, "f32", "resid"), "fc1": (4096, 1024, "gelu", None),
+                 "fc2": (1024, 4096, "f32", "resid"), "patch": (1024, 768, "f32", "pos"), "neck0": (256, 1024, "f32", None)}
+_VIT_L_CASE = {}
+
+
+def _vit_l_case(dev, name, M):
+    """Operands of one ViT-L Linear at M rows (generated on the device, kept for the tile sweep of the same shape)."""
+    if (name, M) not in _VIT_L_CASE:
+        _VIT_L_CASE.clear()
+        N, K, epi, res = VIT_L_LINEARS[name]
+        g = torch.Generator(device=dev).manual_seed(M + N + K)
+        r = lambda shape, sc: torch.randn(shape, generator=g, device=dev) * sc  # noqa: E731
+        a = r((M, K), 1.0).half()
+        w = r((N, K), 0.05).half()
+        bias = r((N,), 0.5)
+        resid = (r((M, N), 1.0) if res == "resid" else r((4096, N), 2.0) + 0.25 if res == "pos" else None)
+        _VIT_L_CASE[(name, M)] = (a, w, bias, resid)
+    return _VIT_L_CASE[(name, M)]
+
+
+def _vit_l_linear(name, a, w, bias, resid):
+    from protosam_amd import ops
+    N, K, epi, res = VIT_L_LINEARS[name]
+    if epi != "f32":
+        return ops.gemm(a, w, bias, epilogue=ops.EPI_F16 if epi == "f16" else ops.EPI_GELU_F16)
+    if res == "resid":
+        x = resid.clone()
+        return ops.gemm(a, w, bias, out=x, epilogue=ops.EPI_F32, resid=x)
+    out = torch.full((a.shape[0], N), float("nan"), device=a.device)
+    if res == "pos":
+        return ops.gemm(a, w, bias, out=out, epilogue=ops.EPI_F32, resid=resid, resid_mod=4096)
+    return ops.gemm(a, w, bias, out=out, epilogue=ops.EPI_F32)
+
+
+def _vit_l_check(name, out, a, w, bias, resid, rows=None):
+    """out (or its `rows`) against the float64 product of the same fp16 operands; returns the max abs error."""
+    N, K, epi, res = VIT_L_LINEARS[name]
+    M = a.shape[0]
+    idx = torch.arange(M, device=a.device) if rows is None else rows
+    ref = a[idx].double() @ w.double().t() + bias.double()
+    if epi == "gelu":
+        ref = torch.nn.functional.gelu(ref)
+    if res == "resid":
+        ref = ref + resid[idx].double()
+    elif res == "pos":
+        ref = ref + resid.double()[idx % 4096]
+    got = out[idx].double()
+    assert torch.isfinite(got).all()
+    err = (got - ref).abs()
+    if epi == "f32":       # fp32 results: the accumulation order only
+        bound = 2e-4 * max(1.0, (K / 1280) ** 0.5) + 1e-5 * ref.abs()
+    else:                  # fp16 results: their rounding (2^-11 relative) plus the accumulation order
+        bound = 2e-3 + 2e-3 * ref.abs()
+    bad = (err > bound).nonzero()
+    assert bad.numel() == 0, f"{name} M={M}: {bad.shape[0]} outputs off, first at {idx[bad[0, 0]].item(), bad[0, 1].item()}: " \
+                             f"{got[bad[0, 0], bad[0, 1]].item()} vs {ref[bad[0, 0], bad[0, 1]].item()}"
+    return err.max().item()
+
+
+@pytest.mark.parametrize("name,M,tile", [(n, M, t) for n in VIT_L_LINEARS for M in (4096, 8192, 3 * 4096) for t in (0, 1, 11, 15, 16)])
+def test_gemm_vit_l_linears(dev, name, M, tile):
+    """SAM ViT-L's Linear layers at one, two and three images (M = 4096 / 8192 / 12288 tokens): qkv (3072 x 1024, fp16), attn.proj
+    (1024 x 1024, fp32 + residual in place), mlp.lin1 (4096 x 1024, GELU), mlp.lin2 (1024 x 4096, fp32 + residual in place), the patch
+    embedding (1024 x 768, + position table, resid_mod 4096) and neck.0 (256 x 1024) - through every tile (auto, 1 / 11 HIP, 15 / 16
+    assembly; a tile that cannot take a shape falls back) against the float64 product of the same fp16 operands, every output."""
+    from protosam_amd import ops
+    a, w, bias, resid = _vit_l_case(dev, name, M)
+    ops.gemm_set_tile(tile)
+    try:
+        out = _vit_l_linear(name, a, w, bias, resid)
+    finally:
+        ops.gemm_set_tile(0)
+    err = _vit_l_check(name, out, a, w, bias, resid)
+    print(f"ViT-L {name} M={M} tile {tile}: max abs err vs float64 {err:.2e}")
+
+
+@pytest.mark.parametrize("name", ["fc1", "fc2"])
+def test_gemm_vit_l_linears_batched(dev, name):
+    """mlp.lin1 / mlp.lin2 of ViT-L at 32 images (M = 131072, the batched headline size): a fixed sample of rows against float64 - the first
+    and last rows of the first and last 256-row tiles among them - and every output finite."""
+    M = 32 * 4096
+    a, w, bias, resid = _vit_l_case(dev, name, M)
+    out = _vit_l_linear(name, a, w, bias, resid)
+    last = (M - 1) // 256 * 256
+    pick = torch.randperm(M, generator=torch.Generator().manual_seed(5))[:120]
+    rows = torch.unique(torch.cat([torch.tensor([0, 255, last, M - 1]), pick])).to(dev)
+    assert torch.isfinite(out.float()).all()
+    err = _vit_l_check(name, out, a, w, bias, resid, rows=rows)
+    _VIT_L_CASE.clear()
+    print(f"ViT-L {name} M={M}: max abs err vs float64 over {rows.numel()} rows {err:.2e}")
+
+
 def test_gemm_row_remap_and_resid_mod(dev):
     """patch-embed style: rows of batch b land at b*stride + off + p, resid (pos-embed) indexed by p."""
     from protosam_amd import ops
@@ -346,7 +440,7 @@ def test_attention_global_spiky_rows(dev):
     torch.testing.assert_close(out.float(), ref, rtol=2e-3, atol=2e-3)
 
 
-@pytest.mark.parametrize("H,hd", [(2, 64), (2, 80)])
+@pytest.mark.parametrize("H,hd", [(2, 64), (2, 80), (16, 64)])     # (16, 64): SAM ViT-L's global blocks
 def test_attention_global_relpos(dev, H, hd):
     from oracle.sam_image_encoder import decomposed_rel_pos_terms
     from protosam_amd import ops
@@ -369,7 +463,8 @@ def test_attention_global_relpos(dev, H, hd):
 
 @pytest.mark.parametrize("B,g,H,hd", [(2, 64, 2, 64), (2, 64, 2, 80), (3, 32, 3, 80), (1, 20, 1, 64), (5, 30, 16, 80),
                                       (1, 24, 2, 80),    # (24 x 24 = 576 tokens: psam_relpos' one-tile-per-wave form)
-                                      (3, 64, 16, 80)])  # (1200 items: several per workgroup of the persistent kernels, every edge class)
+                                      (3, 64, 16, 80),   # (1200 items: several per workgroup of the persistent kernels, every edge class)
+                                      (1, 64, 16, 64), (2, 64, 16, 64), (3, 64, 16, 64)])   # SAM ViT-L: 16 heads of 64
 def test_attention_window_relpos(dev, B, g, H, hd):
     """14x14 windows over a g x g map, zero-padded tokens carry the qkv bias (image_encoder.py:267-271): the two-kernel path
     (psam_relpos -> relq) and the window kernels of the fused path (attn_kernel, wattn_kernel, the assembly kernel of
@@ -417,6 +512,7 @@ def test_attention_window_relpos(dev, B, g, H, hd):
     ref = window_unpartition(o, ws, pad_hw, (g, g)).reshape(B, N, C)
     for name, out in outs.items():
         err = (out.float().cpu() - ref).abs().max().item()
+        print(f"B={B} g={g} H={H} hd={hd} {name}: max err vs reference {err:.2e}")
         assert torch.isfinite(out.float()).all(), name
         torch.testing.assert_close(out.float().cpu(), ref, rtol=2e-3, atol=2e-3, msg=f"{name}: max err {err:.2e}")
 
@@ -507,7 +603,8 @@ def test_window_attention_fused_relpos(dev):
 @pytest.mark.parametrize("mode,N,H,hd,B", [(0, 1297, 12, 64, 2), (0, 200, 3, 80, 1), (1, 4096, 2, 80, 1), (1, 4096, 2, 64, 1), (1, 4096, 8, 80, 1),
                                            (1, 4096, 16, 80, 1), (1, 1024, 8, 80, 2), (1, 512, 8, 80, 1),
                                            (1, 4096, 8, 64, 1), (1, 1024, 12, 64, 2), (1, 4096, 12, 64, 2),    # hd = 64: the ViT-B kernel; 12 heads
-                                           (1, 4096, 12, 64, 1), (1, 1024, 3, 80, 3)])   # B * H = 12 / 9: surplus workgroups of the last eight leave
+                                           (1, 4096, 12, 64, 1), (1, 1024, 3, 80, 3),    # B * H = 12 / 9: surplus workgroups of the last eight leave
+                                           (1, 4096, 16, 64, 1), (1, 4096, 16, 64, 2)])  # SAM ViT-L's global blocks: 16 heads of 64
 def test_attention_softmax_variants_agree(dev, mode, N, H, hd, B):
     """V2 (tree reductions, one rescale decision for both query tiles, row sums on the matrix pipe) against the round-1 serial
     form and the fp32 reference, including rows whose maximum jumps late in the key sequence (the lazy-rescale branch: a key
@@ -536,6 +633,8 @@ def test_attention_softmax_variants_agree(dev, mode, N, H, hd, B):
         finally:
             ops.attention_set_variant(5)
     ref = _ref_attn_global(qkv, B, N, H, hd, scale, rel=rel)
+    print(f"mode {mode} N={N} H={H} hd={hd} B={B}: max err vs fp32 reference of variants 0 / 9 / 17 / default: "
+          + ", ".join(f"{(o - ref).abs().max().item():.2e}" for o in outs))
     for o in outs:
         assert torch.isfinite(o).all()
         torch.testing.assert_close(o, ref, rtol=2e-3, atol=2e-3)
@@ -569,7 +668,8 @@ def test_attention_global_asm_any_token_count(dev, N, H, B):
     assert (out - hip).abs().max().item() < 2e-3
 
 
-@pytest.mark.parametrize("B,H,hd", [(1, 2, 64), (1, 2, 80), (2, 16, 80), (3, 12, 64), (1, 5, 80)])
+@pytest.mark.parametrize("B,H,hd", [(1, 2, 64), (1, 2, 80), (2, 16, 80), (3, 12, 64), (1, 5, 80),
+                                    (1, 16, 64), (2, 16, 64)])     # SAM ViT-L's global blocks: 16 heads of 64, one and two images
 def test_attention_global_fused_relpos(dev, B, H, hd):
     """psam_gattn_asm_{80,64}_fused (round 5): the decomposed rel-pos terms of the global blocks (image_encoder.py:325-372) computed
     inside the attention kernel from the packed tables - against the fp32 reference arithmetic (oracle's restatement of
@@ -582,6 +682,7 @@ def test_attention_global_fused_relpos(dev, B, H, hd):
     assert ops.attention_fused_relpos(B, N, H, hd, g, g)
     qkv = _rand((B, N, 3, H, hd), dev, 1.0, 51)
     qkv[0, N - 100, 1, 0] = qkv[0, 1000, 0, 0] * 6.0
+    qkv[B - 1, N - 7, 1, H - 1] = qkv[B - 1, 3000, 0, H - 1] * 6.0      # (and in the last head of the last image)
     qkv = qkv.half()
     Rh = _rand((2 * g - 1, hd), dev, 0.3, 52)
     Rw = _rand((2 * g - 1, hd), dev, 0.3, 53)
@@ -598,10 +699,30 @@ def test_attention_global_fused_relpos(dev, B, H, hd):
         bias = (rh_ref[..., :, None] + rw_ref[..., None, :]).reshape(B, H, N, N).to(dev)
         ref = _ref_attn_global(qkv, B, N, H, hd, scale, rel=bias)
         torch.testing.assert_close(fused, ref, rtol=2e-3, atol=2e-3)
+    # every (b, h), one [N, N] bias at a time: both paths against the fp32 reference arithmetic, not only against each other (they read
+    # the same packed tables), and the two-kernel path's rel-pos terms themselves
+    q = qkv.float().view(B, N, 3, H, hd)[:, :, 0].permute(0, 2, 1, 3).reshape(B * H, N, hd)
+    rh_ref, rw_ref = decomposed_rel_pos_terms(q.cpu(), Rh.cpu(), Rw.cpu(), (g, g))
+    torch.testing.assert_close(rel_h.cpu().view(B * H, g, g, g), rh_ref, rtol=1e-4, atol=1e-4)
+    torch.testing.assert_close(rel_w.cpu().view(B * H, g, g, g), rw_ref, rtol=1e-4, atol=1e-4)
+    rh_ref, rw_ref = rh_ref.to(dev), rw_ref.to(dev)
+    qkvf = qkv.float().view(B, N, 3, H, hd)
+    worst = {"fused": 0.0, "two-kernel": 0.0}
+    for bh in range(B * H):
+        b, h = divmod(bh, H)
+        bias = (rh_ref[bh][..., :, None] + rw_ref[bh][..., None, :]).reshape(N, N)
+        qh, kh, vh = qkvf[b, :, 0, h], qkvf[b, :, 1, h], qkvf[b, :, 2, h]
+        ref = ((qh * scale) @ kh.t() + bias).softmax(-1) @ vh
+        for name, o in (("fused", fused), ("two-kernel", two)):
+            oh = o.view(B, N, H, hd)[b, :, h]
+            worst[name] = max(worst[name], (oh - ref).abs().max().item())
+            torch.testing.assert_close(oh, ref, rtol=2e-3, atol=2e-3, msg=lambda m: f"{name}, image {b}, head {h}: {m}")
+    print(f"B={B} H={H} hd={hd}: max err vs fp32 reference over every head: fused {worst['fused']:.2e}, two-kernel {worst['two-kernel']:.2e}")
 
 
 @pytest.mark.parametrize("tile", [1, 11, 15])
-@pytest.mark.parametrize("M,D,N2,act", [(4096, 1280, 3840, 0), (1297 * 3, 768, 3072, 1), (777, 256, 256, 0)])
+@pytest.mark.parametrize("M,D,N2,act", [(4096, 1280, 3840, 0), (1297 * 3, 768, 3072, 1), (777, 256, 256, 0),
+                                        (4096, 1024, 3072, 0), (8192, 1024, 4096, 1)])   # SAM ViT-L qkv / lin1: 16 partial sums per row
 def test_gemm_folded_layernorm(dev, tile, M, D, N2, act):
     """psam_gemm_f16_ln: x = resid + gamma * (a w^T + b) emitting half(x) + per-row partial sums, psam_ln_finalize, then the
     consuming GEMM on half(x) with LayerNorm-folded weights  ==  Linear(LayerNorm(x)) (GELU) to fp16-operand accuracy; also
@@ -812,7 +933,7 @@ def test_gemm_f32x3_matches_fp32_accuracy(dev, M, N, K, mode):
     assert err < err_f16 / (10 if mode == "tiny" else 100), (err, err_f16)
 
 
-@pytest.mark.parametrize("M,N,K", [(4096, 1280, 5120), (4096, 1024, 4096), (3000, 1280, 5120)])
+@pytest.mark.parametrize("M,N,K", [(4096, 1280, 5120), (4096, 1024, 4096), (3000, 1280, 5120), (8192, 1024, 4096)])
 @pytest.mark.parametrize("with_ln", [True, False])
 def test_gemm_splitk_asm_residual_layernorm(dev, M, N, K, with_ln):
     """Round 6: x += a w^T + b as K ranges of the assembly tile (psam_gemm_asm_f32_sk: items = (tile, range), partial sums to planes of a
@@ -820,6 +941,7 @@ def test_gemm_splitk_asm_residual_layernorm(dev, M, N, K, with_ln):
     arithmetic, against the one-launch GEMM + LayerNorm pass it replaces, run-to-run identical, and identical when replayed from a graph."""
     from protosam_amd import ops
     ks = ops.gemm_splitk_ranges(M, N, K)
+    print(f"{M}x{N}x{K}: {ks} K ranges")
     assert ks >= 2, ks
     a = _rand((M, K), dev, 1.0, 71).half()
     w = _rand((N, K), dev, 0.02, 72).half()
@@ -840,6 +962,11 @@ def test_gemm_splitk_asm_residual_layernorm(dev, M, N, K, with_ln):
     torch.testing.assert_close(x, ref, rtol=1e-4, atol=3e-4)
     ref16 = torch.nn.functional.layer_norm(x, (N,), lnw, lnb, 1e-6) if with_ln else x
     torch.testing.assert_close(o16.float(), ref16, rtol=2e-3, atol=2e-3)
+    ref64 = (x0.double() + a.double() @ w.double().t() + bias.double())
+    ref16_64 = torch.nn.functional.layer_norm(ref64, (N,), lnw.double(), lnb.double(), 1e-6) if with_ln else ref64
+    e32, e16 = (x.double() - ref64).abs().max().item(), (o16.double() - ref16_64).abs().max().item()
+    print(f"  vs float64: x max err {e32:.2e}, fp16 {'LayerNorm' if with_ln else 'copy'} max err {e16:.2e}")
+    assert e32 < 2e-4 * (K / 1280) ** 0.5
     # the path it replaces: one GEMM launch with the residual epilogue, then the LayerNorm pass (same products, another summation order)
     y = ops.gemm(a, w, bias, out=x0.clone(), epilogue=ops.EPI_F32, resid=x0)
     torch.testing.assert_close(x, y, rtol=1e-5, atol=2e-5)

@@ -93,11 +93,21 @@ def _dice(a, b):
                                 dict(use_bbox=True, use_points=True, point_mode="both", use_cca=True),
                                 dict(use_bbox=False, use_points=True, point_mode="conf", use_cca=False)])
 def test_protosam_forward_vs_oracle(dev, kw):
+    _forward_vs_oracle(dev, "vit_b", 3, 12, kw)
+
+
+def test_protosam_forward_vs_oracle_vit_l_full_depth(dev):
+    """SAM ViT-L with all 24 blocks (global blocks 5 / 11 / 17 / 23) through ProtoSAM.forward against the oracle pipeline, under the
+    bounds of test_protosam_forward_vs_oracle (a small DINOv2 depth: the coarse stage is not what this covers)."""
+    _forward_vs_oracle(dev, "vit_l", None, 2, dict(use_bbox=True, use_points=True, point_mode="both", use_cca=False))
+
+
+def _forward_vs_oracle(dev, sam_type, sam_depth, dino_depth, kw):
     from oracle import alp as oalp, dinov2 as odino, glue
     from protosam_amd.protosam import InputFactory, TYPE_ALPNET
     from protosam_amd.synth import synth_pair, synth_state_dict
-    sam_depth, dino_depth = 3, 12
-    model, alp_sd = _build(dev, f"random:vit_b:1234:{sam_depth}", dino_depth, **kw)
+    spec = f"random:{sam_type}:1234" + ("" if sam_depth is None else f":{sam_depth}")
+    model, alp_sd = _build(dev, spec, dino_depth, **kw)
     sam_sd = {k: v.cpu() for k, v in synth_state_dict(model.sam, 1234).items()}
     s_img, s_m, q_img, q_gt = synth_pair(512, seed=0)
     inp = InputFactory.create_input(TYPE_ALPNET, q_img, support_images=[s_img], support_labels=[s_m], isval=True,
@@ -111,7 +121,7 @@ def test_protosam_forward_vs_oracle(dev, kw):
     enc = lambda im: odino.forward_features(im, enc_sd, "dinov2_b14", depth=dino_depth)["x_norm_patchtokens"]  # noqa
     logits_ref = oalp.fewshot_forward(enc, s_img, s_m, q_img, 512)
     taps = {}
-    pred_ref, scores_ref = glue.protosam_forward(q_img, logits_ref, sam_sd, "vit_b", use_bbox=kw["use_bbox"],
+    pred_ref, scores_ref = glue.protosam_forward(q_img, logits_ref, sam_sd, sam_type, use_bbox=kw["use_bbox"],
                                                  use_points=kw["use_points"], point_mode=kw["point_mode"],
                                                  use_cca=kw["use_cca"], encoder_depth=sam_depth, taps=taps)
     n_ref = 1 if kw["use_cca"] else taps["cc"][0] - 1
@@ -121,7 +131,7 @@ def test_protosam_forward_vs_oracle(dev, kw):
     perr = (torch.sigmoid(low) - torch.sigmoid(low_ref)).abs().max().item()
     d = _dice(pred.cpu(), pred_ref)
     flips = (pred.cpu() != pred_ref).sum().item()
-    print(f"{kw}: comps {n_ref}, max |dprob(low_res)| {perr:.3e}, final Dice {d:.5f}, flipped px {flips}, "
+    print(f"{sam_type} depth {sam_depth} {kw}: comps {n_ref}, max |dprob(low_res)| {perr:.3e}, final Dice {d:.5f}, flipped px {flips}, "
           f"scores {np.abs(np.array(scores) - np.array(scores_ref)).max():.2e}, fg frac {pred_ref.mean():.3f}")
     assert d >= 0.999
     assert perr < 1e-3          # the north-star tolerance on the output probability map
@@ -261,11 +271,24 @@ def test_forward_batch_overlapped_streams_same_result(dev):
 def test_forward_batch_skips_sam_for_empty_slices(dev, mask_only):
     """A slice whose coarse mask is empty never reaches SAM (ProtoSAM.py:612-613 returns before set_image): in a batch only
     the non-empty slices are encoded, and every slice still equals its per-slice forward."""
-    from protosam_amd.protosam import InputFactory, TYPE_ALPNET
-    from protosam_amd.synth import synth_pair
     kw = dict(use_bbox=False, use_points=False, use_mask=True) if mask_only else \
         dict(use_bbox=True, use_points=True, point_mode="both")
-    model, _ = _build(dev, "random:vit_b:1234:2", 2, **kw)
+    _skips_sam_for_empty_slices(dev, "random:vit_b:1234:2", kw)
+
+
+@pytest.mark.parametrize("splitk", [False, True])
+def test_forward_batch_sub_batch_vit_l(dev, splitk):
+    """The same with SAM ViT-L (6 blocks): the two non-empty slices are encoded at B = 2, and the per-slice forwards that follow run at
+    B = 1 on views of that workspace - also with `splitk_lin2`, where ViT-L takes mlp.lin2 in split-K form at both batch sizes."""
+    _skips_sam_for_empty_slices(dev, "random:vit_l:1234:6", dict(use_bbox=True, use_points=True, point_mode="both"), splitk=splitk)
+
+
+def _skips_sam_for_empty_slices(dev, sam_spec, kw, splitk=False):
+    from protosam_amd.protosam import InputFactory, TYPE_ALPNET
+    from protosam_amd.synth import synth_pair
+    model, _ = _build(dev, sam_spec, 2, **kw)
+    if splitk:
+        model.sam.image_encoder.splitk_lin2 = True
     s_img, s_m, q0, _ = synth_pair(512, seed=0)
     _, _, q1, _ = synth_pair(512, seed=3)
     _, _, q2, _ = synth_pair(512, seed=5)
@@ -300,6 +323,8 @@ def test_forward_batch_skips_sam_for_empty_slices(dev, mask_only):
             pb, sb = batched[b]
             # (the one-slice call takes other GEMM kernels - 128-tile / split-K - than the batch: rounding-level differences
             # flip a few border pixels of the ~20 000-pixel mask)
+            print(f"{sam_spec} splitk_lin2={splitk} slice {b}: {(pb != p1).sum().item()} pixels differ from the per-slice forward, "
+                  f"scores {sb} / {s1}")
             assert pb.shape == p1.shape and (pb != p1).sum().item() <= 32
             assert len(sb) == len(s1) and np.allclose(np.array(sb, dtype=np.float64), np.array(s1, dtype=np.float64), atol=2e-3)
         calls.clear()

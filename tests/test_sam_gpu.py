@@ -23,14 +23,34 @@ def _image(seed=0):
     return q.to(torch.uint8)  # [1,3,1024,1024]
 
 
-@pytest.mark.parametrize("model_type,depth", [("vit_b", 3), ("vit_h", 8)])
-def test_image_encoder(dev, model_type, depth):
+def _normalised(img):
+    return (img.float() - torch.tensor([123.675, 116.28, 103.53]).view(1, 3, 1, 1)) / torch.tensor([58.395, 57.12, 57.375]).view(1, 3, 1, 1)
+
+
+@pytest.fixture(scope="module")
+def oracle_embedding():
+    """(model_type, depth, image seed) -> the fp32 CPU oracle's embedding [1,256,64,64] of _image(seed) under _sam's default weights
+    (seed 1234), computed once per module (one ViT-L image of 6 blocks: a few seconds on the CPU)."""
     from oracle import sam_image_encoder as oenc
+    from protosam_amd.synth import synth_state_dict
+    from protosam_amd.segment_anything import sam_model_registry
+    cache = {}
+
+    def get(model_type, depth, seed):
+        if (model_type, depth, seed) not in cache:
+            sd = synth_state_dict(sam_model_registry[model_type](encoder_depth=depth), 1234)
+            cache[(model_type, depth, seed)] = oenc.image_encoder(_normalised(_image(seed)), sd, model_type=model_type, depth=depth)
+        return cache[(model_type, depth, seed)]
+    return get
+
+
+@pytest.mark.parametrize("model_type,depth", [("vit_b", 3), ("vit_h", 8),
+                                              ("vit_l", 6)])    # ViT-L: windowed blocks 0-4 and the global block 5, 16 heads of 64
+def test_image_encoder(dev, oracle_embedding, model_type, depth):
     sam, sd = _sam(dev, model_type, depth)
     img = _image(1)
-    x = (img.float() - torch.tensor([123.675, 116.28, 103.53]).view(1, 3, 1, 1)) / torch.tensor(
-        [58.395, 57.12, 57.375]).view(1, 3, 1, 1)
-    ref = oenc.image_encoder(x, sd, model_type=model_type, depth=depth)
+    x = _normalised(img)
+    ref = oracle_embedding(model_type, depth, 1)
     xin = sam.preprocess(img.to(dev))
     torch.testing.assert_close(xin.cpu(), x, rtol=1e-6, atol=1e-6)
     out = sam.image_encoder(xin)
@@ -196,15 +216,13 @@ def test_image_encoder_rel_pos_table_resize(dev):
     assert err.max() < 5e-2 and err.mean() < 3e-3
 
 
-def test_image_encoder_folded_layernorm_path(dev):
+@pytest.mark.parametrize("model_type,depth", [("vit_b", 3), ("vit_l", 6)])
+def test_image_encoder_folded_layernorm_path(dev, oracle_embedding, model_type, depth):
     """`fold_ln = True` (LayerNorm folded into the GEMMs either side of it, psam_gemm_f16_ln) against the oracle and against
     the default path with the separate LayerNorm passes."""
-    from oracle import sam_image_encoder as oenc
-    sam, sd = _sam(dev, "vit_b", 3)
+    sam, sd = _sam(dev, model_type, depth)
     img = _image(4)
-    x = (img.float() - torch.tensor([123.675, 116.28, 103.53]).view(1, 3, 1, 1)) / torch.tensor(
-        [58.395, 57.12, 57.375]).view(1, 3, 1, 1)
-    ref = oenc.image_encoder(x, sd, model_type="vit_b", depth=3)
+    ref = oracle_embedding(model_type, depth, 4)
     xin = sam.preprocess(img.to(dev))
     outs = {}
     default = sam.image_encoder.fold_ln
@@ -216,7 +234,7 @@ def test_image_encoder_folded_layernorm_path(dev):
     sam.image_encoder.fold_min_fill = 0.8
     for fold, o in outs.items():
         err = (o - ref).abs()
-        print(f"fold_ln={fold}: max abs err {err.max():.3e} mean {err.mean():.3e}")
+        print(f"{model_type} depth {depth} fold_ln={fold}: max abs err {err.max():.3e} mean {err.mean():.3e}")
         assert err.max() < 5e-2 and err.mean() < 3e-3
     assert (outs[True] - outs[False]).abs().max() < 5e-2
 
@@ -252,7 +270,7 @@ def test_image_encoder_split_fp16_neck_and_patch_embedding(dev):
         assert errs[True].mean() <= errs[False].mean() * (0.25 if depth == 0 else 1.02)
 
 
-@pytest.mark.parametrize("model_type,depth", [("vit_b", 3), ("vit_h", 4)])
+@pytest.mark.parametrize("model_type,depth", [("vit_b", 3), ("vit_h", 4), ("vit_l", 6)])
 def test_image_encoder_reference_width_mode(dev, model_type, depth):
     """Round 6 (`gemm_x3`, PSAM_ENCODER_X3=1): every Linear of the blocks at fp32 accuracy (fp32 operands and results, psam_gemm_f32x3),
     LayerNorm / GELU as fp32 passes, split neck + exact-pixel patch embedding; only QK^T / PV keep fp16 operands. Against the fp32 oracle
@@ -284,19 +302,20 @@ def test_image_encoder_reference_width_mode(dev, model_type, depth):
     torch.testing.assert_close(ops.gelu_f32_(g.clone()), torch.nn.functional.gelu(g), rtol=1e-6, atol=1e-6)
 
 
-def test_image_encoder_splitk_lin2_option(dev):
-    """`splitk_lin2` (PSAM_SPLITK_LIN2=1, round 6): one ViT-H image with mlp.lin2 as K ranges of the assembly tile and the next block's norm1
+@pytest.mark.parametrize("model_type,depth", [("vit_h", 3), ("vit_l", 6)])
+def test_image_encoder_splitk_lin2_option(dev, oracle_embedding, model_type, depth):
+    """`splitk_lin2` (PSAM_SPLITK_LIN2=1, round 6): one image with mlp.lin2 as K ranges of the assembly tile and the next block's norm1
     fused into the reduce pass (ops.gemm_splitk_ln) - same products in another summation order: the embedding agrees with the default path
     far inside the fp16-operand error, and with the oracle as well as the default does; eager and graph replay agree bit for bit."""
-    from oracle import sam_image_encoder as oenc
     from protosam_amd import ops
-    sam, sd = _sam(dev, "vit_h", 3)
+    sam, sd = _sam(dev, model_type, depth)
     enc = sam.image_encoder
-    assert ops.gemm_splitk_ranges(4096, 1280, 5120) >= 2
+    D = enc.embed_dim
+    ks = ops.gemm_splitk_ranges(4096, D, 4 * D)
+    print(f"{model_type}: mlp.lin2 of one image in {ks} K ranges")
+    assert ks >= 2
     img = _image(7)
-    x = (img.float() - torch.tensor([123.675, 116.28, 103.53]).view(1, 3, 1, 1)) / torch.tensor(
-        [58.395, 57.12, 57.375]).view(1, 3, 1, 1)
-    ref = oenc.image_encoder(x, sd, model_type="vit_h", depth=3)
+    ref = oracle_embedding(model_type, depth, 7)
     xin = sam.preprocess(img.to(dev))
     outs = {}
     for sk in (False, True):
@@ -307,7 +326,57 @@ def test_image_encoder_splitk_lin2_option(dev):
     assert torch.equal(a, outs[True])
     d = (outs[True] - outs[False]).abs().max().item()
     e0, e1 = (outs[False] - ref).abs(), (outs[True] - ref).abs()
-    print(f"splitk_lin2: max |difference to the default path| {d:.2e}; vs oracle: default max {e0.max():.3e} mean {e0.mean():.3e}, split-K max {e1.max():.3e} mean {e1.mean():.3e}")
+    print(f"{model_type} depth {depth} splitk_lin2: max |difference to the default path| {d:.2e}; vs oracle: default max {e0.max():.3e} mean {e0.mean():.3e}, split-K max {e1.max():.3e} mean {e1.mean():.3e}")
     # (another fp32 summation order flips fp16 roundings of the LayerNorm outputs downstream: the two paths differ from each other by what
     # either differs from the oracle - measured 2.1e-3 against 3.7e-3 / 3.6e-3)
     assert d < 5e-3 and e1.mean() < 1.05 * e0.mean() + 1e-6 and e1.max() < 5e-2
+
+
+def test_image_encoder_two_images_vit_l(dev, oracle_embedding):
+    """ViT-L (6 blocks) on a [2,3,1024,1024] batch: M = 8192 rows pick other GEMM kernels than one image does, so each image has to meet the
+    oracle bounds on its own, and agree with its own one-image call to within the fp16-operand error (not bit for bit)."""
+    sam, sd = _sam(dev, "vit_l", 6)
+    enc = sam.image_encoder
+    seeds = (1, 4)
+    imgs = torch.cat([_image(s) for s in seeds]).to(dev)
+    two = enc(sam.preprocess(imgs)).cpu().clone()
+    assert two.shape == (2, 256, 64, 64)
+    for i, s in enumerate(seeds):
+        one = enc(sam.preprocess(imgs[i:i + 1])).cpu().clone()
+        ref = oracle_embedding("vit_l", 6, s)[0]
+        e2, e1, d = (two[i] - ref).abs(), (one[0] - ref).abs(), (two[i] - one[0]).abs()
+        print(f"vit_l depth 6 image {i} of 2: max abs err {e2.max():.3e} mean {e2.mean():.3e}; alone: max {e1.max():.3e} mean {e1.mean():.3e}; "
+              f"batch vs alone max {d.max():.3e} mean {d.mean():.3e}")
+        assert e2.max() < 5e-2 and e2.mean() < 3e-3 and e1.max() < 5e-2 and e1.mean() < 3e-3
+        assert d.max() < 5e-2 and d.mean() < 3e-3
+
+
+def test_image_encoder_splitk_lin2_sub_batches_vit_l(dev, oracle_embedding):
+    """Regression: with `splitk_lin2` on, ViT-L takes mlp.lin2 in split-K form at one image AND at two (more K ranges for one image), and the
+    one-image workspace is built as views of the two-image one. A B = 2, B = 1, B = 2 sequence must give, call by call, bit for bit what a
+    freshly built encoder with the same weights gives at that batch size alone (same kernels, same ks), and meet the oracle bounds. (The
+    one-image call once inherited a truncated view of the two-image split-K scratch and failed gemm_splitk_ln's size check.)"""
+    from protosam_amd import ops
+    D, N = 1024, 4096
+    ks = {B: ops.gemm_splitk_ranges(B * N, D, 4 * D) for B in (1, 2)}
+    print(f"vit_l mlp.lin2 K ranges: {ks}")
+    assert ks[1] >= 2 and ks[2] >= 2
+    seeds = (1, 4)
+    imgs = torch.cat([_image(s) for s in seeds])
+    sam, sd = _sam(dev, "vit_l", 6)
+    enc = sam.image_encoder
+    enc.splitk_lin2 = True
+    x = {2: sam.preprocess(imgs.to(dev)), 1: sam.preprocess(imgs[:1].to(dev))}
+    got = [(B, enc(x[B]).cpu().clone()) for B in (2, 1, 2)]
+    alone = {}
+    for B in (2, 1):
+        fresh, _ = _sam(dev, "vit_l", 6)
+        fresh.image_encoder.splitk_lin2 = True
+        alone[B] = fresh.image_encoder(x[B]).cpu().clone()
+        del fresh
+    for i, (B, out) in enumerate(got):
+        assert torch.equal(out, alone[B]), (i, B, (out - alone[B]).abs().max().item())
+        for b in range(B):
+            e = (out[b] - oracle_embedding("vit_l", 6, seeds[b])[0]).abs()
+            print(f"call {i} (B = {B}) image {b}: max abs err {e.max():.3e} mean {e.mean():.3e}")
+            assert e.max() < 5e-2 and e.mean() < 3e-3
