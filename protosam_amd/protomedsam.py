@@ -18,10 +18,8 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .protosam import DECODER_CHUNK, MAX_COMPONENTS, ModelWrapper, ProtoSAM, class_support_scores
+from .protosam import CCL_SLOTS, DECODER_CHUNK, MAX_COMPONENTS, ModelWrapper, ProtoSAM, class_support_scores
 from .segment_anything import sam_model_registry
-
-CCL_SLOTS = 32   # planes per connected-components launch chain of the batched paths (~8 MB of CCL scratch per slot at 1024^2)
 
 
 class ProtoMedSAM(nn.Module):

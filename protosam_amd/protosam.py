@@ -29,6 +29,7 @@ Unsupported (outside SURVEY §8's hot path, raise NotImplementedError): `debug` 
 """
 import os
 from abc import ABC, abstractmethod
+from functools import partial
 
 import numpy as np
 import torch
@@ -53,9 +54,7 @@ MAX_COMPONENTS = 256          # fast path: table rows per slice that travel D2H 
 MAX_COMPONENTS_LARGE = 4096   # psam_ccl's limit; used for a slice that overflows the fast table
 DECODER_CHUNK = 256           # prompt sets per decoder call (workspace ~ 25 MB per prompt set)
 MAX_NEG_COMPONENTS = 64   # psam_neg_points launches one tile grid per component
-
-
-CCL_SLOTS = 32            # planes per connected-components launch chain of forward_classes_batch (~8 MB of scratch per slot)
+CCL_SLOTS = 32            # planes per connected-components launch chain of the batched paths (~8 MB of scratch per slot at 1024^2)
 
 
 def plan_class_prompts(B, C, plane_sets, feat_row):
@@ -310,8 +309,6 @@ class ProtoSAM(nn.Module):
             self._mask_vals = tuple(float(v) for v in np.array([10.0, -8.0], dtype=np.float32).astype(np.uint8))
         if tuple(self.image_size) != (1024, 1024):
             raise NotImplementedError("image_size must be (1024, 1024) as in validation_protosam.py:220")
-        self._ccl = None
-        self._bufs = {}
         self.last_stats = {}
         # The SAM image encoder does not depend on the coarse model: on a second HIP stream it shares the GPU with DINOv2 + ALP +
         # connected components, whose small launches and part-filled rounds then cost nothing. Round 2 measured no gain (107.0 / 110.3
@@ -547,21 +544,32 @@ class ProtoSAM(nn.Module):
         # predictor.predict: apply_coords with original_size == 1024 is the identity; torch.as_tensor(dtype=float)
         return coords, labels, rows
 
-    def _work_buffers(self, dev, B):
-        key = (str(dev), B)
-        if key not in self._bufs:
-            self._bufs[key] = dict(
-                fg_sum=torch.zeros(B, dtype=torch.int32, device=dev),
-                prob=torch.empty((B, 2, 1024, 1024), dtype=torch.float32, device=dev),
-                pred=torch.empty((B, 1024, 1024), dtype=torch.uint8, device=dev),
-                q1024=torch.empty((B, 3, 1024, 1024), dtype=torch.float32, device=dev),
-                mm=torch.empty(2 * B, dtype=torch.int32, device=dev),
-                patches=torch.empty((B * 4096, 768), dtype=torch.float16, device=dev),
-                fg_host=torch.zeros(B, dtype=torch.int32).pin_memory(), fg_event=torch.cuda.Event(),
-                event=torch.cuda.Event(), sam_done=torch.cuda.Event())
-        if self._ccl is None or self._ccl.slots < B:
-            self._ccl = ops.CclWorkspace(1024, 1024, MAX_COMPONENTS, dev, slots=max(B, 1))
-        return self._bufs[key]
+    def _batch_bufs(self, dev, P, B):
+        """Buffers of `_segment`, grown to the largest P (planes) / B (slices) seen: per plane both softmax channels, the arg-max
+        map, the foreground count, the component table (pinned), the negative-point keys and 256^2 labels; per slice the encoder
+        input (`_sam_features`' keys); one connected-components workspace of min(P, CCL_SLOTS) slots."""
+        S = self.sam.image_encoder.img_size
+        bb = self.__dict__.setdefault("_bbufs", {})
+        if bb.get("P", 0) < P:
+            bb.update(P=P, prob=None, pred=None, lab256=None)      # (drop the old planes before allocating the larger ones)
+            bb.update(prob=torch.empty((P, 2, S, S), dtype=torch.float32, device=dev),
+                      pred=torch.empty((P, S, S), dtype=torch.uint8, device=dev),
+                      fg_sum=torch.zeros(P, dtype=torch.int32, device=dev), fg_host=torch.zeros(P, dtype=torch.int32).pin_memory(),
+                      tabs_host=torch.empty((P, ops.CC_HDR + ops.CC_STRIDE * MAX_COMPONENTS), dtype=torch.float64).pin_memory(),
+                      neg_keys=torch.empty((P, MAX_NEG_COMPONENTS + 1), dtype=torch.int64, device=dev),
+                      neg_keys_host=torch.empty((P, MAX_NEG_COMPONENTS + 1), dtype=torch.int64).pin_memory(),
+                      lab256=torch.empty((P, S // 4, S // 4), dtype=torch.int32, device=dev) if self._mask_only else None,
+                      fg_event=torch.cuda.Event(), event=torch.cuda.Event(), sam_done=torch.cuda.Event())
+        if bb.get("B", 0) < B:
+            bb.update(B=B, q1024=None, patches=None)
+            bb.update(q1024=torch.empty((B, 3, S, S), dtype=torch.float32, device=dev),
+                      mm=torch.empty(2 * B, dtype=torch.int32, device=dev),
+                      patches=torch.empty((B * 4096, 768), dtype=torch.float16, device=dev))
+        slots = min(P, CCL_SLOTS)
+        if bb.get("ccl") is None or bb["ccl"].slots < slots:
+            bb["ccl"] = None
+            bb["ccl"] = ops.CclWorkspace(S, S, MAX_COMPONENTS, dev, slots=slots)
+        return bb
 
     def _ccl_large(self, pred, pfg, fg_sum):
         """One plane (pred uint8 [H,W], foreground probability pfg fp32 [H,W], its foreground count fg_sum int32 [1]) with more
@@ -634,201 +642,186 @@ class ProtoSAM(nn.Module):
         M = B*tokens rows, the mask decoder sees all components of all slices at once). `coarse_model_input`: one input (all
         slices share its support set) or a list of (input, n) pairs in batch order (the first n slices belong to the first support
         set, ...: both encoders, the connected components, SAM and the decoder do not depend on the support; only the prototype
-        match does). Slices never interact, so each result equals the per-slice `forward`. Returns a list of (pred, scores)."""
-        B = query_images.shape[0]
-        original_size = query_images.shape[-2]
+        match does). Slices never interact, so each result equals the per-slice `forward`. Returns a list of (pred, scores); the
+        masks of prompted slices are views of one float32 [B,H,W] tensor. Pipeline: `_segment` with one class."""
+        B, H = query_images.shape[0], query_images.shape[-2]
         dev = query_images.device
         if self.coarse_pred_only:                                               # ProtoSAM.py:580-590: nothing of SAM runs
-            return self._coarse_only_batch(self._coarse_logits(query_images, coarse_model_input, degrees_rotate), original_size)
-        bufs = self._work_buffers(dev, B)
-        sam = self.sam
-        S = sam.image_encoder.img_size
-        # 0. The SAM image encoder depends on the query image only, not on the coarse model: with `overlap_streams` it is
-        #    enqueued on a second HIP stream so the two ViTs share the GPU (optional, see __init__)
+            return self._coarse_only_batch(self._coarse_logits(query_images, coarse_model_input, degrees_rotate), H)
+        bb = self._batch_bufs(dev, B, B)
+        S = self.sam.image_encoder.img_size
+        # The SAM image encoder depends on the query image only, not on the coarse model: with `overlap_streams` it is enqueued
+        # on a second HIP stream so the two ViTs share the GPU (optional, see __init__)
         main = torch.cuda.current_stream(dev)
         mode = self.overlap_streams
         if isinstance(mode, str):
             mode = True if mode == "1" else False if mode == "0" else (self._dense_run >= 4 and STAGE_TIMER is None and not ops.TIMERS and ops.GEMM_TIMER is None)
-        side = self._side_stream(dev) if mode else None
         feat_tok = None
-        if side is not None:
+        if mode:
+            side = self._side_stream(dev)
             side.wait_stream(main)                                              # inputs / earlier work on `main` are visible
             with torch.cuda.stream(side):
-                feat_tok = self._sam_features(query_images, bufs, B, S)
-                bufs["sam_done"].record(side)
+                feat_tok = self._sam_features(query_images, bb, B, S)
+                bb["sam_done"].record(side)
         _mark("start")
         output_logits = self._coarse_logits(query_images, coarse_model_input, degrees_rotate)   # [B,2,H,W]
         _mark("coarse: DINOv2 + ALP")
-        # 1. (bilinear to 1024) -> softmax -> argmax                               ProtoSAM.py:592-602
-        bufs["fg_sum"].zero_()
-        output_p, pred = ops.prob_argmax(output_logits.float().contiguous(), S, S, prob=bufs["prob"], pred=bufs["pred"],
-                                         fg_sum=bufs["fg_sum"])
-        bufs["fg_host"].copy_(bufs["fg_sum"], non_blocking=True)                # foreground pixel count per slice
-        bufs["fg_event"].record()
-        # 2. connected components + per-component statistics; the tables go to pinned host memory asynchronously
-        cw = self._ccl
-        ops.ccl_batch(pred[:B], output_p[:B], cw, fg_sum=bufs["fg_sum"])        # one chain of six launches for the batch
-        for b in range(B):
-            if self.use_neg_points:
-                nk = bufs.setdefault("neg_keys", torch.empty((B, MAX_NEG_COMPONENTS + 1), dtype=torch.int64, device=dev))
-                ops.neg_points(cw, output_p[b, 0], cw.tabs[b], MAX_NEG_COMPONENTS, keys=nk[b], labels=cw.labels_b[b])
-            if self._mask_only:   # cv2.resize(mask, (256, 256), INTER_NEAREST) samples pixel (4y, 4x)
-                bufs.setdefault("lab256", torch.empty((B, S // 4, S // 4), dtype=torch.int32, device=dev))[b].copy_(
-                    cw.labels_b[b].view(S, S)[::4, ::4])
-        cw.tabs_host[:B].copy_(cw.tabs[:B], non_blocking=True)
-        if self.use_neg_points:
-            nkh = bufs.setdefault("neg_keys_host", torch.empty((B, MAX_NEG_COMPONENTS + 1), dtype=torch.int64).pin_memory())
-            nkh.copy_(bufs["neg_keys"], non_blocking=True)
-        bufs["event"].record()
-        _mark("softmax / argmax + connected components")
-        # 3./4. image hand-off + SAM image encoder (already running on the side stream, or enqueued here before the host looks
-        #       at the component tables)
-        #       A slice whose coarse mask is empty never reaches SAM (ProtoSAM.py:612-613 returns before `set_image`): only the
-        #       non-empty slices are encoded. The foreground counts arrive while the CCL kernels above keep the GPU busy.
-        feat_row = list(range(B))                                               # slice -> row of feat_tok
-        if feat_tok is None:
-            bufs["fg_event"].synchronize()
-            keep = [b for b in range(B) if int(bufs["fg_host"][b]) > 0]
-            if len(keep) == B:
-                feat_tok = self._sam_features(query_images, bufs, B, S)
-            elif keep:
-                sub = query_images[torch.tensor(keep, device=dev)]
-                feat_tok = self._sam_features(sub, bufs, len(keep), S)
-                feat_row = [-1] * B
-                for i, b in enumerate(keep):
-                    feat_row[b] = i
-        _mark("image hand-off + SAM image encoder")
-        # 5. host: number of components and prompts per slice
-        bufs["event"].synchronize()
-        if side is not None:
-            main.wait_event(bufs["sam_done"])                                   # the decoder below consumes feat_tok on `main`
-            feat_tok.record_stream(main)
-        tabs = cw.tabs_host[:B].numpy()
+        # (bilinear to 1024) -> softmax -> argmax                                  ProtoSAM.py:592-602
+        out, res, tabs, st = self._segment(query_images, 1, partial(ops.prob_argmax, output_logits.float().contiguous(), S, S),
+                                           feat_tok=feat_tok)
         # (what "auto" overlap looks at next time)
-        self._dense_run = self._dense_run + 1 if all(int(tabs[b][0]) > 0 for b in range(B)) else 0
-        results = [None] * B
-        coords, labels, img_idx, slice_idx, spans = [], [], [], [], []   # img_idx: row of feat_tok, slice_idx: slice
-        stats = []
-        for b in range(B):
-            tab = tabs[b]
-            overflow = int(tab[0]) > int(tab[1])
-            if overflow:
-                # more components than the fast table holds (cv2 + the reference's per-component loop have no limit,
-                # util/utils.py:474-494, ProtoSAM.py:505): redo this slice with the large table, and refresh what was derived
-                # from the truncated labelling
-                big, tab = self._ccl_large(pred[b], output_p[b, 1], bufs["fg_sum"][b:b + 1])
-                if self._mask_only:
-                    bufs["lab256"][b].copy_(big.labels.view(S, S)[::4, ::4])
-            n_found, n = int(tab[0]), int(tab[1])
-            stats.append(dict(n_components=n_found, fg_pixels=int(tab[2]), n_prompts=0))
-            if n == 0:                                                          # ProtoSAM.py:612-613
-                results[b] = (output_p[b].argmax(dim=0), [0])
+        self._dense_run = self._dense_run + 1 if all(int(tab[0]) > 0 for tab in tabs) else 0
+        masks = out.view(B, H, H).float()                                       # the {0., 1.} of psam_mask_union
+        results, stats = [], []
+        for b, tab in enumerate(tabs):
+            stats.append(dict(n_components=int(tab[0]), fg_pixels=int(tab[2]), n_prompts=st["spans"].get((b, 0), (0, 0))[1]))
+            if (b, 0) not in st["prompt"]:                                      # ProtoSAM.py:612-613
+                results.append((bb["prob"][b].argmax(dim=0), [0]))
                 continue
-            if self._mask_only:
-                # component k of the table carries label k + 1 (csrc/ccl.hip); cca keeps the most confident one
-                ids = [int(tab[3]) + 1] if self.use_cca else list(range(1, n + 1))
-                spans.append((b, len(img_idx), len(ids)))
-                labels += ids
-                img_idx += [feat_row[b]] * len(ids)
-                slice_idx += [b] * len(ids)
-                stats[b].update(n_prompts=len(ids))
-                continue
-            neg_keys = None
-            if self.use_neg_points:
-                neg_keys = bufs["neg_keys_host"][b].numpy()
-                if n > MAX_NEG_COMPONENTS or n_found > MAX_COMPONENTS:
-                    # the fast path asked for the rings of the first MAX_NEG_COMPONENTS components of the fast table only (one
-                    # tile grid per component): ask again for all of them, on the labelling the table in hand belongs to
-                    # (the reference walks every component, ProtoSAM.py:395-419)
-                    ws = big if overflow else cw
-                    neg_keys = ops.neg_points(ws, output_p[b, 0], ws.tabs[0] if overflow else cw.tabs[b], n,
-                                              labels=None if overflow else cw.labels_b[b]).cpu().numpy()
-            topk = None
-            if self.num_points_for_sam > 1 and self.use_points and self.point_mode in (CONF_MODE, BOTH_MODE):
-                ids = [int(tab[3]) + 1] if self.use_cca else list(range(1, n + 1))
-                topk = self._topk_points(output_p[b, 1], big.labels if overflow else cw.labels_b[b], S, ids,
-                                         self.num_points_for_sam)
-            c, l, rows = self._prompts_from_table(tab, neg_keys, topk)
-            spans.append((b, len(img_idx), len(l)))
-            coords += c
-            labels += l
-            img_idx += [feat_row[b]] * len(l)
-            stats[b].update(n_prompts=len(l), table=rows, prompts=(c, l))
+            results.append((masks[b], res[b][0][1]))
+            if not self._mask_only:
+                stats[b].update(table=st["tables"][(b, 0)], prompts=st["prompts"][(b, 0)])
         self.last_stats = stats[0] if B == 1 else dict(per_slice=stats)
-        if spans and self._mask_only:
-            # 6m. mask prompts: dense embedding per component, no sparse prompts, best of the three masks
-            #     (get_sam_input_mask :452-466, predict_w_masks :468-498)
-            P = len(labels)
-            masks, iou = self._decode_mask_sets(feat_tok, bufs["lab256"], slice_idx, labels, img_idx)
-            best = iou[:, 1:].argmax(dim=1)                                               # score.argmax(), :494
-            chosen = masks[torch.arange(P, device=dev), best + 1].unsqueeze(1).contiguous()   # [P,1,256,256]
-            iou_host = iou[:, 1:].max(dim=1).values.cpu().numpy()
-            for (b, start, cnt) in spans:
-                out = ops.mask_union(chosen[start:start + cnt], 0, S, original_size, sam.variant_id(), sam.mask_threshold)
-                results[b] = (out, [np.float32(v) for v in iou_host[start:start + cnt]])
-            self.last_stats.update(low_res=masks, iou=iou, best=best, spans=spans)
-        elif spans:
-            # 6. batched two-way decoder over all components of all slices (ProtoSAM.py:500-527)
-            masks, iou = self._decode_point_sets(feat_tok, coords, labels, img_idx)
-            sel = 0 if self.use_cca else 1                                      # multimask_output = not use_cca; index 0
-            _mark("prompt encoder + mask decoder")
-            iou_host = iou[:, sel].cpu().numpy()
-            for (b, start, cnt) in spans:
-                # 7. upsample -> > 0 -> union over components -> nearest to the input size   ProtoSAM.py:669-676
-                out = ops.mask_union(masks[start:start + cnt], sel, S, original_size, sam.variant_id(),
-                                     sam.mask_threshold)
-                results[b] = (out, [np.float32(v) for v in iou_host[start:start + cnt]])
-            _mark("post-processing (upsample, threshold, union)")
-            if B == 1:
-                self.last_stats.update(low_res=masks, iou=iou, sel=sel)
-            else:
-                self.last_stats.update(low_res=masks, iou=iou, sel=sel, spans=spans)
+        if st["low_res"] is not None:
+            self.last_stats.update({k: st[k] for k in ("low_res", "iou", "sel", "best") if k in st},
+                                   spans=[(b, first, cnt) for (b, _), (first, cnt) in st["spans"].items()])
         return results
 
-    def _class_bufs(self, dev, P, B):
-        """Buffers of `forward_classes_batch`, grown to the largest P (planes) / B (slices) seen: per plane both softmax channels,
-        the arg-max map, the foreground count, the component table (pinned), the negative-point keys and 256^2 labels; per slice
-        the encoder input (`_sam_features`' keys)."""
-        S = self.sam.image_encoder.img_size
-        cb = self.__dict__.setdefault("_cbufs", {})
-        if cb.get("P", 0) < P:
-            cb.update(P=P, prob=None, pred=None, lab256=None)      # (drop the old planes before allocating the larger ones)
-            cb.update(prob=torch.empty((P, 2, S, S), dtype=torch.float32, device=dev),
-                      pred=torch.empty((P, S, S), dtype=torch.uint8, device=dev),
-                      fg_sum=torch.zeros(P, dtype=torch.int32, device=dev), fg_host=torch.zeros(P, dtype=torch.int32).pin_memory(),
-                      tabs_host=torch.empty((P, ops.CC_HDR + ops.CC_STRIDE * MAX_COMPONENTS), dtype=torch.float64).pin_memory(),
-                      neg_keys=torch.empty((P, MAX_NEG_COMPONENTS + 1), dtype=torch.int64, device=dev),
-                      neg_keys_host=torch.empty((P, MAX_NEG_COMPONENTS + 1), dtype=torch.int64).pin_memory(),
-                      lab256=torch.empty((P, S // 4, S // 4), dtype=torch.int32, device=dev) if self._mask_only else None,
-                      fg_event=torch.cuda.Event(), event=torch.cuda.Event())
-        if cb.get("B", 0) < B:
-            cb.update(B=B, q1024=None, patches=None)
-            cb.update(q1024=torch.empty((B, 3, S, S), dtype=torch.float32, device=dev),
-                      mm=torch.empty(2 * B, dtype=torch.int32, device=dev),
-                      patches=torch.empty((B * 4096, 768), dtype=torch.float16, device=dev))
-        slots = min(P, CCL_SLOTS)
-        if getattr(self, "_ccl_chunk", None) is None or self._ccl_chunk.slots < slots:
-            self._ccl_chunk = None
-            self._ccl_chunk = ops.CclWorkspace(S, S, MAX_COMPONENTS, dev, slots=slots)
-        return cb
+    def _segment(self, query_images, C, coarse, out=None, feat_tok=None):
+        """The pipeline under `forward_batch` (C = 1) and `forward_classes_batch`: B query slices [B,3,H,W] and P = C*B class-major
+        planes (plane c*B + b is class c of slice b). `coarse(prob=, pred=, fg_sum=)`: the caller's one launch that writes every
+        plane's softmax, arg-max map and foreground count -> connected components in chunks of CCL_SLOTS planes, each chunk's
+        negative points (psam_neg_points_batch) and 256^2 labels taken before the next chunk overwrites its labels -> ONE SAM
+        encoder forward of the slices where some plane has foreground (ProtoSAM.py:612-613 returns before set_image for an empty
+        coarse mask), enqueued before the host first waits for a table so that the wait overlaps it -> the prompt sets of every
+        plane -> the batched decoder -> ONE psam_mask_union_seg into uint8 [B,C,H,W] (`out` if given; zeros where a plane has no
+        prompt). `feat_tok`: the encoder output of all B slices, already enqueued on the side stream (done at bufs["sam_done"]).
+        Returns (out, results[b][c] = (out[b, c], scores) or (out[b, c], [0]), the host component table of every plane (the large
+        one where the plane overflowed the fast one), stats: forward_classes_batch's `last_stats`, and per pair `tables`, the
+        table rows behind its prompt sets)."""
+        B, H = query_images.shape[0], query_images.shape[-2]
+        P = C * B
+        dev = query_images.device
+        sam = self.sam
+        S = sam.image_encoder.img_size
+        bb = self._batch_bufs(dev, P, B)
+        prob, pred, fg = bb["prob"][:P], bb["pred"][:P], bb["fg_sum"][:P]
+        fg.zero_()
+        coarse(prob=prob, pred=pred, fg_sum=fg)
+        bb["fg_host"][:P].copy_(fg, non_blocking=True)                        # foreground pixel count per plane
+        bb["fg_event"].record()
+        # connected components in chunks of planes; whatever reads a chunk's labels (host top-k, the ring search beyond the fast
+        # key rows) runs before the next chunk overwrites them
+        cw, pending = bb["ccl"], feat_tok is not None
+        need_labels = self.use_neg_points or (self.num_points_for_sam > 1 and self.use_points
+                                              and self.point_mode in (CONF_MODE, BOTH_MODE))
+        tabs_h, keys_h = bb["tabs_host"][:P], bb["neg_keys_host"][:P]
+        sets, keep = {}, None
+        for c0 in range(0, P, cw.slots):
+            c1 = min(c0 + cw.slots, P)
+            n = c1 - c0
+            ops.ccl_batch(pred[c0:c1], prob[c0:c1], cw, fg_sum=fg[c0:c1])
+            if self.use_neg_points:
+                ops.neg_points_batch(cw.labels_b[:n], prob[c0:c1, 0], cw.tabs[:n], MAX_NEG_COMPONENTS, keys=bb["neg_keys"][c0:c1])
+                keys_h[c0:c1].copy_(bb["neg_keys"][c0:c1], non_blocking=True)
+            if self._mask_only:   # cv2.resize(mask, (256, 256), INTER_NEAREST) samples pixel (4y, 4x): one copy per chunk
+                bb["lab256"][c0:c1].copy_(cw.labels_b[:n].view(n, S, S)[:, ::4, ::4])
+            tabs_h[c0:c1].copy_(cw.tabs[:n], non_blocking=True)
+            bb["event"].record()
+            if keep is None and (need_labels or c1 == P):
+                _mark("softmax / argmax + connected components")
+                keep = list(range(B))
+                if not pending:
+                    # the foreground counts arrive while the connected components keep the GPU busy
+                    bb["fg_event"].synchronize()
+                    fgh = bb["fg_host"][:P].view(C, B)
+                    keep = [b for b in range(B) if int(fgh[:, b].max()) > 0]
+                    if keep:
+                        sub = query_images if len(keep) == B else query_images[torch.tensor(keep, device=dev)]
+                        feat_tok = self._sam_features(sub, bb, len(keep), S)
+                _mark("image hand-off + SAM image encoder")
+            if need_labels:
+                bb["event"].synchronize()
+                for i in range(n):
+                    tab = tabs_h[c0 + i].numpy()
+                    if int(tab[0]) <= int(tab[1]) and int(tab[1]) > 0:    # (overflow: relabelled below; empty: no prompt)
+                        sets[c0 + i] = self._plane_prompts(tab, prob[c0 + i], keys_h[c0 + i].numpy(), cw, i)
+        # host: the prompt sets of the other planes
+        bb["event"].synchronize()
+        tabs = []
+        for p in range(P):
+            tab, big = tabs_h[p].numpy(), None
+            if int(tab[0]) > int(tab[1]):
+                # more components than the fast table holds (cv2 + the reference's per-component loop have no limit,
+                # util/utils.py:474-494, ProtoSAM.py:505): this plane again with the large table, and what was derived from the
+                # truncated labelling again
+                big, tab = self._ccl_large(pred[p], prob[p, 1], fg[p:p + 1])
+                if self._mask_only:
+                    bb["lab256"][p].copy_(big.labels.view(S, S)[::4, ::4])
+            tabs.append(tab)
+            if int(tab[1]) > 0 and p not in sets:
+                sets[p] = self._plane_prompts(tab, prob[p], None, big)
+        feat_row = [-1] * B                                                     # slice -> row of feat_tok
+        for i, b in enumerate(keep):
+            feat_row[b] = i
+        prompts = {(p % B, p // B): s[:2] for p, s in sets.items()}
+        plan = plan_class_prompts(B, C, prompts, feat_row)
+        if pending:
+            main = torch.cuda.current_stream(dev)
+            main.wait_event(bb["sam_done"])                                     # the decoder below consumes feat_tok on `main`
+            feat_tok.record_stream(main)
+        # the batched decoder over every prompt set (ProtoSAM.py:500-527); mask prompts: a dense embedding per component, no sparse
+        # prompts, the best of the three masks (get_sam_input_mask :452-466, predict_w_masks :468-498)
+        masks = iou = best = low = None
+        sel, sel_u = (0 if self.use_cca else 1), 0                             # multimask_output = not use_cca; index 0
+        if plan["labels"]:
+            if self._mask_only:
+                masks, iou = self._decode_mask_sets(feat_tok, bb["lab256"], plan["plane_idx"], plan["labels"], plan["img_idx"])
+                best = iou[:, 1:].argmax(dim=1)                                               # score.argmax(), :494
+                low = masks[torch.arange(len(plan["labels"]), device=dev), best + 1].unsqueeze(1).contiguous()
+                scores = iou[:, 1:].max(dim=1).values
+            else:
+                masks, iou = self._decode_point_sets(feat_tok, plan["coords"], plan["labels"], plan["img_idx"])
+                low, sel_u, scores = masks, sel, iou[:, sel]
+            _mark("prompt encoder + mask decoder")
+            scores_h = scores.cpu().numpy()
+        # upsample -> > 0 -> union over each plane's prompt sets -> nearest to the input size          ProtoSAM.py:669-676
+        if out is None:
+            out = torch.empty((B, C, H, H), dtype=torch.uint8, device=dev)
+        assert out.shape == (B, C, H, H) and out.dtype == torch.uint8 and out.is_contiguous()
+        segs = torch.from_numpy(plan["segs"]).to(dev)
+        ops.mask_union_seg(low, sel_u, segs, P, S, H, sam.variant_id(), sam.mask_threshold, out=out.view(P, H, H))
+        _mark("post-processing (upsample, threshold, union)")
+        results = [[(out[b, c], [0]) for c in range(C)] for b in range(B)]
+        for (b, c), (first, cnt) in plan["spans"].items():
+            results[b][c] = (out[b, c], [np.float32(v) for v in scores_h[first:first + cnt]])
+        stats = dict(n_slices=B, n_classes=C, prompt=plan["prompt"], spans=plan["spans"], n_prompted=len(plan["prompt"]),
+                     n_encoded=len(keep), n_components=[[int(tabs[c * B + b][0]) for c in range(C)] for b in range(B)],
+                     prompts=prompts, tables={(p % B, p // B): s[2] for p, s in sets.items()}, low_res=masks, iou=iou, sel=sel)
+        if best is not None:
+            stats.update(best=best)
+        return out, results, tabs, stats
 
-    def _plane_prompts(self, p, tab, labels, pbg, pfg, neg_keys, ws=None, slot=0):
-        """One plane's prompt sets from its component table, as `forward_batch` builds them for a slice: `labels` / `ws` the
-        labelling the table belongs to (ws, slot: its workspace and table row, for negative points beyond the fast key rows),
-        pbg / pfg its softmax channels, neg_keys its fast negative-point keys. -> (coords or None, labels)."""
+    def _plane_prompts(self, tab, prob, neg_keys, ws=None, slot=0):
+        """One plane's prompt sets from its component table: prob [2,S,S] its softmax, neg_keys its fast negative-point keys, ws /
+        slot the workspace and table row of the labelling the table belongs to (read by the host top-k and by the ring search of
+        all components). -> (coords or None, labels, table rows) as `_prompts_from_table` (coords None for mask prompts, where
+        labels are component ids)."""
         S = self.sam.image_encoder.img_size
         n_found, n = int(tab[0]), int(tab[1])
+        # component k of the table carries label k + 1 (csrc/ccl.hip); cca keeps the most confident one
         ids = [int(tab[3]) + 1] if self.use_cca else list(range(1, n + 1))
         if self._mask_only:
-            return None, ids
+            return None, ids, None
         if self.use_neg_points and (n > MAX_NEG_COMPONENTS or n_found > MAX_COMPONENTS):
-            # the rings of all n components (the fast keys hold the first MAX_NEG_COMPONENTS; forward_batch does the same)
-            neg_keys = ops.neg_points(ws, pbg, ws.tabs[slot], n, labels=labels).cpu().numpy()
+            # the fast keys hold the rings of the first MAX_NEG_COMPONENTS components of the fast table only (one tile grid per
+            # component): ask again for all of them, on the labelling the table in hand belongs to (the reference walks every
+            # component, ProtoSAM.py:395-419)
+            neg_keys = ops.neg_points(ws, prob[0], ws.tabs[slot], n, labels=ws.labels_b[slot]).cpu().numpy()
         topk = None
         if self.num_points_for_sam > 1 and self.use_points and self.point_mode in (CONF_MODE, BOTH_MODE):
-            topk = self._topk_points(pfg, labels, S, ids, self.num_points_for_sam)
-        c, l, _ = self._prompts_from_table(tab, neg_keys, topk)
-        return c, l
+            topk = self._topk_points(prob[1], ws.labels_b[slot], S, ids, self.num_points_for_sam)
+        return self._prompts_from_table(tab, neg_keys, topk)
 
     @torch.no_grad()
     def forward_classes_batch(self, query_images, support_image=None, support_masks=None, val_wsize=2, out=None, degrees_rotate=0,
@@ -839,9 +832,8 @@ class ProtoSAM(nn.Module):
         of one [B,C,H,W] tensor (`out` if given), zeros and [0] for a pair whose coarse mask is empty.
         Pipeline: ONE DINOv2 forward of the B slices matched against the C banks (FewShotSeg.class_scores, class-major planes
         c*B + b at grid resolution) -> ONE psam_scores_prob_argmax over the P = C*B planes (both resizes, softmax, arg-max) ->
-        connected components in chunks of CCL_SLOTS planes, each chunk's negative points (psam_neg_points_batch), 256^2 labels and
-        table taken before the next chunk overwrites its labels -> ONE SAM encoder forward of the slices where some class has
-        foreground -> the prompt sets of every (slice, class) -> the batched decoder -> ONE psam_mask_union_seg into [B,C,H,W].
+        `_segment`: the connected components in chunks of CCL_SLOTS planes, ONE SAM encoder forward of the slices where some class
+        has foreground, the prompt sets of every (slice, class), the batched decoder, ONE psam_mask_union_seg into [B,C,H,W].
         `last_stats`: prompt / spans ((b, c) -> rows of low_res), prompts ((b, c) -> its prompt sets), n_prompted, n_encoded,
         n_components [B][C], low_res, iou, sel.
         `supports=` (instead of support_image / support_masks): one support spec per class, what `forward_batch` takes as
@@ -858,15 +850,15 @@ class ProtoSAM(nn.Module):
         else:
             sc, (IH, IW) = self._shared_support_scores(alp, query_images, support_image, support_masks, val_wsize)
         C, B, gh, gw = sc.shape[0], sc.shape[1], sc.shape[-2], sc.shape[-1]
-        P = C * B
-        sc = sc.view(P, 2, gh, gw)
-        H = query_images.shape[-2]
-        dev = query_images.device
+        sc = sc.view(C * B, 2, gh, gw).contiguous()
         if self.coarse_pred_only:                       # ProtoSAM.py:580-590 per plane
-            res = self._coarse_only_batch(ops.bilinear_nchw(sc.contiguous(), IH, IW), H)
+            res = self._coarse_only_batch(ops.bilinear_nchw(sc, IH, IW), query_images.shape[-2])
             self.last_stats = dict(n_slices=B, n_classes=C)
             return [[res[c * B + b] for c in range(C)] for b in range(B)]
-        return self._classes_segment(query_images, sc, C, B, IH, IW, out)
+        S = self.sam.image_encoder.img_size
+        # bilinear to the image size -> bilinear to 1024 -> softmax -> argmax, every plane in one launch   ProtoSAM.py:592-602
+        _, results, _, self.last_stats = self._segment(query_images, C, partial(ops.scores_prob_argmax, sc, IH, IW, S, S), out=out)
+        return results
 
     @staticmethod
     def _shared_support_scores(alp, query_images, support_image, support_masks, val_wsize):
@@ -885,113 +877,6 @@ class ProtoSAM(nn.Module):
             raise TypeError("forward_classes_batch needs a coarse model with class_scores (ALPNetWrapper(FewShotSeg))")
         sc = alp.class_scores(support_image, support_masks, query_images, isval=True, val_wsize=val_wsize)   # [C,B,2,g,g]
         return sc, tuple(support_image.shape[-2:])    # (the image size FewShotSeg.forward resizes its logits to)
-
-    def _classes_segment(self, query_images, sc, C, B, IH, IW, out):
-        """forward_classes_batch after the coarse scores sc [P,2,g,g] (plane c*B + b), whatever support form produced them"""
-        P = C * B
-        H = query_images.shape[-2]
-        dev = query_images.device
-        sam = self.sam
-        S = sam.image_encoder.img_size
-        cb = self._class_bufs(dev, P, B)
-        prob, pred, fg = cb["prob"][:P], cb["pred"][:P], cb["fg_sum"][:P]
-        # 1. bilinear to the image size -> bilinear to 1024 -> softmax -> argmax, every plane in one launch   ProtoSAM.py:592-602
-        fg.zero_()
-        ops.scores_prob_argmax(sc.contiguous(), IH, IW, S, S, prob=prob, pred=pred, fg_sum=fg)
-        cb["fg_host"][:P].copy_(fg, non_blocking=True)
-        cb["fg_event"].record()
-        # 2. connected components in chunks of planes; whatever reads a chunk's labels runs before the next chunk overwrites them
-        cw = self._ccl_chunk
-        need_topk = self.num_points_for_sam > 1 and self.use_points and self.point_mode in (CONF_MODE, BOTH_MODE)
-        tabs_h, keys_h = cb["tabs_host"][:P], cb["neg_keys_host"][:P]
-        plane_sets, found, slow = {}, [0] * P, set()
-        for c0 in range(0, P, cw.slots):
-            c1 = min(c0 + cw.slots, P)
-            n = c1 - c0
-            ops.ccl_batch(pred[c0:c1], prob[c0:c1], cw, fg_sum=fg[c0:c1])
-            if self.use_neg_points:
-                ops.neg_points_batch(cw.labels_b[:n], prob[c0:c1, 0], cw.tabs[:n], MAX_NEG_COMPONENTS, keys=cb["neg_keys"][c0:c1])
-                keys_h[c0:c1].copy_(cb["neg_keys"][c0:c1], non_blocking=True)
-            if self._mask_only:   # cv2.resize(mask, (256, 256), INTER_NEAREST) samples pixel (4y, 4x): one copy per chunk
-                cb["lab256"][c0:c1].copy_(cw.labels_b[:n].view(n, S, S)[:, ::4, ::4])
-            tabs_h[c0:c1].copy_(cw.tabs[:n], non_blocking=True)
-            if need_topk or self.use_neg_points:
-                # host top-k and the negative points of planes beyond the fast key rows read this chunk's labels: now
-                cb["event"].record()
-                cb["event"].synchronize()
-                for i in range(n):
-                    p = c0 + i
-                    tab = tabs_h[p].numpy()
-                    if int(tab[0]) > int(tab[1]) or int(tab[1]) == 0:
-                        continue                        # (overflow: relabelled below; empty: no prompt)
-                    b, c = p % B, p // B
-                    plane_sets[(b, c)] = self._plane_prompts(p, tab, cw.labels_b[i], prob[p, 0], prob[p, 1], keys_h[p].numpy(),
-                                                             cw, i)
-                    slow.add(p)
-        cb["event"].record()
-        # 3. SAM image encoder on the slices where some class has foreground (ProtoSAM.py:612-613 returns before set_image for
-        #    an empty coarse mask), enqueued before the host waits for the tables
-        cb["fg_event"].synchronize()
-        fgh = cb["fg_host"][:P].view(C, B)
-        keep = [b for b in range(B) if int(fgh[:, b].max()) > 0]
-        feat_row, feat_tok = [-1] * B, None
-        if keep:
-            sub = query_images if len(keep) == B else query_images[torch.tensor(keep, device=dev)]
-            feat_tok = self._sam_features(sub, cb, len(keep), S)
-            for i, b in enumerate(keep):
-                feat_row[b] = i
-        # 4. host: the prompt sets of every (slice, class)
-        cb["event"].synchronize()
-        for p in range(P):
-            b, c = p % B, p // B
-            tab = tabs_h[p].numpy()
-            found[p] = int(tab[0])
-            if p in slow:
-                continue
-            if int(tab[0]) > int(tab[1]):
-                # more components than the fast table holds: this plane again with the large table, as forward_batch does
-                big, tab = self._ccl_large(pred[p], prob[p, 1], fg[p:p + 1])
-                if self._mask_only:
-                    cb["lab256"][p].copy_(big.labels.view(S, S)[::4, ::4])
-                if int(tab[1]) > 0:
-                    plane_sets[(b, c)] = self._plane_prompts(p, tab, big.labels, prob[p, 0], prob[p, 1], None, big, 0)
-                continue
-            if int(tab[1]) == 0:
-                continue
-            plane_sets[(b, c)] = self._plane_prompts(p, tab, None, prob[p, 0], prob[p, 1], None)   # (no labels needed here)
-        plan = plan_class_prompts(B, C, plane_sets, feat_row)
-        # 5. the batched decoder over every (slice, class) prompt set
-        masks = iou = None
-        sel = 0 if self.use_cca else 1                  # multimask_output = not use_cca; index 0
-        if plan["labels"]:
-            if self._mask_only:
-                masks, iou = self._decode_mask_sets(feat_tok, cb["lab256"], plan["plane_idx"], plan["labels"], plan["img_idx"])
-                best = iou[:, 1:].argmax(dim=1)                                               # score.argmax(), :494
-                low = masks[torch.arange(len(plan["labels"]), device=dev), best + 1].unsqueeze(1).contiguous()
-                scores_h = iou[:, 1:].max(dim=1).values.cpu().numpy()
-                sel_u = 0
-            else:
-                masks, iou = self._decode_point_sets(feat_tok, plan["coords"], plan["labels"], plan["img_idx"])
-                low, sel_u = masks, sel
-                scores_h = iou[:, sel].cpu().numpy()
-        # 6. upsample -> threshold -> union over each pair's prompts -> nearest to the input size, into [B,C,H,W]
-        if out is None:
-            out = torch.empty((B, C, H, H), dtype=torch.uint8, device=dev)
-        assert out.shape == (B, C, H, H) and out.dtype == torch.uint8 and out.is_contiguous()
-        segs = torch.from_numpy(plan["segs"]).to(dev)
-        if plan["labels"]:
-            ops.mask_union_seg(low, sel_u, segs, P, S, H, sam.variant_id(), sam.mask_threshold, out=out.view(P, H, H))
-        else:
-            ops.mask_union_seg(None, 0, segs, P, S, H, sam.variant_id(), sam.mask_threshold, out=out.view(P, H, H))
-        results = [[(out[b, c], [0]) for c in range(C)] for b in range(B)]
-        for (b, c), (first, cnt) in plan["spans"].items():
-            results[b][c] = (out[b, c], [np.float32(v) for v in scores_h[first:first + cnt]])
-        self.last_stats = dict(n_slices=B, n_classes=C, prompt=plan["prompt"], spans=plan["spans"], n_prompted=len(plan["prompt"]),
-                               n_encoded=len(keep), n_components=[[found[c * B + b] for c in range(C)] for b in range(B)],
-                               prompts=plane_sets, low_res=masks, iou=iou, sel=sel)
-        if self._mask_only and masks is not None:
-            self.last_stats.update(best=best)
-        return results
 
     def _decode_point_sets(self, feat_tok, coords, labels, img_idx):
         """Point / box prompt sets (`_prompts_from_table`'s coords and labels, one set per row) on image img_idx[i] of feat_tok
