@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: query-slices/sec (512x512), end-to-end ProtoSAM inference (BASELINE.json).
 
-  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
       N > 1 without a launcher: this process stays off the GPU and starts N fresh ranks itself
       (python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py ...),
       relays rank 0's JSON line and exits with the ranks' status. Under a launcher (WORLD_SIZE in the
@@ -12,13 +12,17 @@ DINOv2 ViT-B/14 encoder + ALP prototype match + SAM ViT-H image encoder + prompt
 512x512 slices of a synthetic CT-like volume, seeded random weights, reference default flags (use_bbox, use_points,
 point_mode='both', use_cca=False). A "step" is one pass of `ProtoSAM.forward` over a batch of `--batch` query slices
 (default 32) per rank, followed by the all-gather of the step's uint8 masks. Inputs are resident in HBM when the timed region starts.
-Support features / prototype banks are cached per z-part (values identical to the reference's per-slice re-encode,
-SURVEY Q18); the line also carries the reference-shaped numbers: `per_slice_forward` (one `ProtoSAM.forward` per slice, what
-validation_protosam.py:387 does) and `no_support_cache` (support re-encoded for every slice, grid_proto_fewshot.py:181-184).
+Support features / prototype banks are cached per z-part (values identical to the reference's per-slice re-encode).
 
-Prints ONE JSON line on rank 0, with `ms_per_step` (wall time of one of the K timed steps), `roofline` (dominant kernel = the
-MFMA GEMM, timed live with HIP events on its own stream), `roofline_hbm` (the HBM-bound kernels: achieved algorithmic GB/s), per-stage times, and `cpu_baseline` (the CPU
-oracle on a bounded sample of the same workload, timed on this host's cores at all cores and at 1 thread).
+A plain run does only what the headline needs: it sets up, warms up, times the K steps, writes `--dump-outputs` and prints ONE
+JSON line on rank 0, with `ms_per_step` (wall time of one of the K timed steps), `roofline` (dominant kernel = the MFMA GEMM,
+priced live with HIP events on every third timed step) and `power_clock` (both gathered during the timed steps themselves).
+`--full` (world 1) adds the legs that take runs of their own, after the timed steps: `roofline_hbm` (the HBM-bound kernels:
+achieved algorithmic GB/s), per-stage times, the stream-overlap A/B, the reference-shaped numbers `per_slice_forward` (one
+`ProtoSAM.forward` per slice, what validation_protosam.py:387 does) and `no_support_cache` (support re-encoded for every slice,
+grid_proto_fewshot.py:181-184), `sparse_volume`, `reference_width`, `rank_of_8_strong`, `other_configs` (BASELINE configs 2 / 3 / 5)
+and `cpu_baseline` (the CPU oracle on a bounded sample of the same workload, timed on this host's cores at all cores and at 1
+thread) with `parity_vs_cpu_oracle`. `--no-extras`, `--no-other-configs` and `--no-cpu-baseline` leave legs out of a `--full` run.
 """
 import argparse
 import json
@@ -58,14 +62,17 @@ def parse_args(argv=None):
     ap.add_argument("--sam", default="vit_h", choices=["vit_b", "vit_l", "vit_h"])
     ap.add_argument("--slices", type=int, default=64)
     ap.add_argument("--no-support-cache", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the per-slice / no-cache / stage / HBM-roofline legs")
+    ap.add_argument("--full", action="store_true", help="after the headline, also run the legs that take runs of their own (world 1): "
+                    "per-stage and HBM-roofline timings, the other call patterns, precisions and configs, the CPU baseline and its parity")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU baseline and parity legs of a --full run")
+    ap.add_argument("--no-extras", action="store_true", help="skip the GPU legs of a --full run (per-slice, no-cache, "
+                    "stage, HBM-roofline, rank-of-8, other configs)")
     ap.add_argument("--cpu-slices", type=int, default=3, help="slices of the CPU baseline at all cores")
     ap.add_argument("--cpu-1thread-slices", type=int, default=1, help="slices of the CPU baseline at 1 thread, as the reference "
                     "runs (validation_protosam.py:299: one slice takes about a minute); 0 skips it")
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"], help="weak: --batch slices per rank per step; strong: "
                     "a step is ONE pass over the --slices volume, rank r takes z = r (mod world) (SURVEY 8e), one all-gather per step")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the BASELINE configs 2 / 3 / 5 legs of the default run")
+    ap.add_argument("--no-other-configs", action="store_true", help="skip the BASELINE configs 2 / 3 / 5 legs of a --full run")
     ap.add_argument("--cpu-sam-depth", type=int, default=None, help="debug: truncate both models' SAM depth")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step "
                     "returned as DIR/<name>.npy (see dump_outputs)")
@@ -467,14 +474,14 @@ def main(argv=None, runtime=None):
         "roofline": roofline,
         "power_clock": power_clock,
     }
-    if world == 1 and not args.no_extras:     # single-GPU legs (they would need the other ranks for the all-gather otherwise)
+    if world == 1 and args.full and not args.no_extras:     # single-GPU legs (they would need the other ranks for the all-gather otherwise)
         res.update(extras(args, model, step, ops, psmod, B, torch, dev))
         if not strong:
             res["rank_of_8_strong"] = rank_of_8(args, model, vol_d, sup_imgs, sup_masks, dev, torch)
         if not args.no_other_configs:
             res["other_configs"] = other_configs(args, dev, torch, ops)
     cpu = parity = None
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         # (rank 0 at N = 1 only, after every timed region of the run)
         cpu, parity = cpu_baseline(model, alp_sd, vol, svol, slab, args, dev)
     res["cpu_baseline"] = cpu

@@ -305,3 +305,29 @@ def test_bench_dump_outputs_world1(tmp_path, monkeypatch):
     assert len(rows) == 63 and list(rows) == sorted(set(rows)) and rows[-1] < 80
     assert big["slice_z"].tolist() == [r["last_zs"][i] for i in rows]
     assert all(np.array_equal(big["masks"][k], _fake_mask512(r["last_zs"][i]).numpy()) for k, i in enumerate(rows))
+
+
+def test_bench_plain_run_skips_the_full_legs(monkeypatch):
+    """A plain `bench.py` run at world 1 is setup, warm-up, the timed steps and the line: none of the legs that take runs of their
+    own (extras, rank of 8, other configs, CPU baseline) start; `--full` runs every one of them, and the `--no-*` switches still
+    leave theirs out of a `--full` run."""
+    import bench
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+        monkeypatch.delenv(k, raising=False)
+    ran = []
+    monkeypatch.setattr(bench, "extras", lambda *a: ran.append("extras") or {"per_slice_forward": {}})
+    monkeypatch.setattr(bench, "rank_of_8", lambda *a: ran.append("rank_of_8") or {})
+    monkeypatch.setattr(bench, "other_configs", lambda *a: ran.append("other_configs") or {})
+    monkeypatch.setattr(bench, "cpu_baseline", lambda *a: ran.append("cpu_baseline") or ({"value": 1.0}, {"slices": []}))
+    argv = ["--steps", "2", "--warmup", "1", "--batch", "4", "--micro", "4", "--slices", "24"]
+    rt = _CountingRuntime()
+    line = bench.main(argv, runtime=rt)["line"]
+    assert ran == [] and rt.step_calls == 1 + 2 and line["steps"] == 2 and line["ms_per_step"] > 0
+    assert line["cpu_baseline"] is None and "per_slice_forward" not in line and "parity_vs_cpu_oracle" not in line
+    assert not bench.parse_args(argv).full and bench.parse_args(argv + ["--full"]).full
+    line = bench.main(argv + ["--full"], runtime=_CountingRuntime())["line"]
+    assert ran == ["extras", "rank_of_8", "other_configs", "cpu_baseline"]
+    assert line["cpu_baseline"] == {"value": 1.0} and "per_slice_forward" in line and "parity_vs_cpu_oracle" in line
+    ran.clear()
+    bench.main(argv + ["--full", "--no-other-configs", "--no-cpu-baseline"], runtime=_CountingRuntime())
+    assert ran == ["extras", "rank_of_8"]
