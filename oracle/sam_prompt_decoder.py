@@ -54,7 +54,7 @@ def _ln2d(x, w, b, eps=1e-6):
 def embed_masks(sd, masks, pre="prompt_encoder."):
     """prompt_encoder.py:51-59,102-105: masks [B,1,256,256] -> [B,256,64,64]."""
     m = pre + "mask_downscaling."
-    x = F.conv2d(masks.float(), sd[m + "0.weight"], sd[m + "0.bias"], stride=2)
+    x = F.conv2d(masks.to(sd[m + "0.weight"].dtype), sd[m + "0.weight"], sd[m + "0.bias"], stride=2)   # (float64 weights: float64)
     x = F.gelu(_ln2d(x, sd[m + "1.weight"], sd[m + "1.bias"]))
     x = F.conv2d(x, sd[m + "3.weight"], sd[m + "3.bias"], stride=2)
     x = F.gelu(_ln2d(x, sd[m + "4.weight"], sd[m + "4.bias"]))

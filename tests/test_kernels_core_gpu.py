@@ -931,6 +931,7 @@ def test_gemm_f32x3_matches_fp32_accuracy(dev, M, N, K, mode):
     if mode != "tiny":
         assert err < 8 * 2.0 ** -22, (err, err_exact, err_f16)
     assert err < err_f16 / (10 if mode == "tiny" else 100), (err, err_f16)
+    assert err_exact < 8 * 2.0 ** -22, (err, err_exact, err_f16)      # the exact-fp32 MFMA kernel (psam_gemm_f32) it stands in for
 
 
 @pytest.mark.parametrize("M,N,K", [(4096, 1280, 5120), (4096, 1024, 4096), (3000, 1280, 5120), (8192, 1024, 4096)])
