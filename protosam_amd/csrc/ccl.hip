@@ -166,9 +166,10 @@ __device__ __forceinline__ float ord2f32(uint32_t u) {
 __global__ __launch_bounds__(256) void ccl_stats_kernel(const int* __restrict__ parent, int H, int W,
                                                         const float* __restrict__ pfg, int* __restrict__ labels,
                                                         int* __restrict__ acc_i, unsigned long long* __restrict__ acc_u,
-                                                        double* __restrict__ acc_d, CclStride st) {
+                                                        double* __restrict__ acc_d, int* counters, CclStride st) {
   parent += blockIdx.z * st.parent; pfg += blockIdx.z * st.pfg; labels += blockIdx.z * st.labels;
   acc_i += blockIdx.z * st.acc_i; acc_u += blockIdx.z * st.acc_u; acc_d += blockIdx.z * st.acc_d;
+  counters += blockIdx.z * st.counters;
   const int x = blockIdx.x * blockDim.x + threadIdx.x;
   const int lane = threadIdx.x & 63;
   const int y0 = blockIdx.y * STAT_ROWS, y1 = min(y0 + STAT_ROWS, H);
@@ -176,6 +177,7 @@ __global__ __launch_bounds__(256) void ccl_stats_kernel(const int* __restrict__ 
   int pl = 0, pcnt = 0, pmnx = 0, pmny = 0, pmxx = 0, pmxy = 0;
   unsigned long long psx = 0, psy = 0, pkey = 0;
   double pps = 0.0;
+  int dropped = 0;   // foreground pixels of components beyond the table's capacity (label 0), for sum(pred) without fg_sum
   auto flush = [&]() {
     if (pl != 0 && lane == 0) {
       const int k = pl - 1;
@@ -195,15 +197,18 @@ __global__ __launch_bounds__(256) void ccl_stats_kernel(const int* __restrict__ 
     int lab = 0;
     float pv = 0.f;
     int p = 0;
+    bool fg = false;
     if (x < W) {
       p = y * W + x;
       const int r = parent[p];
       if (r >= 0) {
         lab = (r == p) ? labels[p] : labels[r];  // roots were labelled by ccl_rank_kernel (0 if beyond capacity)
         pv = pfg[p];
+        fg = true;
       }
       if (r != p) labels[p] = lab;               // never rewrites a root's label (read by other threads)
     }
+    dropped += __popcll(__ballot(fg && lab == 0));
     unsigned long long todo = __ballot(lab != 0);
     while (todo) {
       const int leader = __ffsll((long long)todo) - 1;
@@ -237,6 +242,7 @@ __global__ __launch_bounds__(256) void ccl_stats_kernel(const int* __restrict__ 
     }
   }
   flush();
+  if (dropped && lane == 0) atomicAdd(&counters[1], dropped);
 }
 
 __global__ void ccl_finalize_kernel(const int* counters, int cap, int W, const int* __restrict__ acc_i,
@@ -252,7 +258,8 @@ __global__ void ccl_finalize_kernel(const int* counters, int cap, int W, const i
     long long tot = 0;
     if (fg_sum) {
       tot = fg_sum[0];
-    } else {
+    } else {  // the kept components' areas plus the pixels of those beyond the capacity
+      tot = counters[1];
       for (int k = 0; k < n; ++k) tot += acc_i[k * 5];
     }
     total_s = (double)tot;
@@ -314,7 +321,7 @@ static int ccl_launch(const void* pred, const float* pfg, int H, int W, int cap,
   hipLaunchKernelGGL(ccl_rank_kernel, dim3(1, 1, Z), dim3(256), cap * sizeof(int), s, roots, cap, counters, labels, acc_i,
                      (unsigned long long*)acc_u, acc_d, st);
   hipLaunchKernelGGL(ccl_stats_kernel, dim3((W + 255) / 256, (H + STAT_ROWS - 1) / STAT_ROWS, Z), dim3(256), 0, s, parent, H, W, pfg, labels,
-                     acc_i, (unsigned long long*)acc_u, acc_d, st);
+                     acc_i, (unsigned long long*)acc_u, acc_d, counters, st);
   hipLaunchKernelGGL(ccl_finalize_kernel, dim3(1, 1, Z), dim3(256), 0, s, counters, cap, W, acc_i,
                      (const unsigned long long*)acc_u, acc_d, fg_sum, tab, st);
   return psam_launch_status();
