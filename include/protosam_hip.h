@@ -298,6 +298,22 @@ int psam_mask_binarize(const float* low, const int* idx, int n, int IN, int MID,
  * automatic_mask_generator.py:221-316; utils/amg.py:156-176, 303-346 */
 int psam_plane_stats(const float* planes, int n, int H, int W, float thr, float off, int* stats, void* out, void* stream);
 
+/* Scoring: confusion counts and boxes of n (prediction plane, label plane) pairs in one launch, exact (integer atomics).
+ * rows int32 [n,4] = (pred plane, pred value, label plane, label value); pixel i of a row is predicted iff
+ * pred[pred plane][i] == pred value and true iff label[label plane][i] == label value (float planes compare by value).
+ * pred / label: [planes, H, W] with contiguous planes `*_stride` ELEMENTS apart, element type `*_dtype` as vol_dtype below
+ * (0 int16, 1 float32, 2 uint8, 3 int32); element-aligned, no other alignment asked for.
+ * out int64 [n,12], columns in this order:
+ *   0 tp, 1 fp, 2 fn, 3 tn, 4 pred x0, 5 pred y0, 6 pred x1, 7 pred y1, 8 gt x0, 9 gt y0, 10 gt x1, 11 gt y1
+ * (inclusive extremes; an empty set gives x0 = y0 = INT_MAX, x1 = y1 = -1, as psam_mask_stats). A row whose pred plane is
+ * outside [0, pred_planes) or whose label plane is outside [0, label_planes) is skipped: its out row keeps these initial values
+ * with four zero counts, and nothing is read for it. n >= 1 (no 65535 limit), H, W >= 1, H * W < 2^31 - 4096.
+ * Replaces validation_protosam.py:49-62 (get_bounding_box), :169-185 (get_dice_iou_precision_recall), :400-409 (their use per
+ * slice) and util/metric.py:50-107 (Metric.record), all of which work on a host copy of the mask. */
+int psam_seg_counts(const void* pred, int pred_dtype, int pred_planes, long long pred_stride, const void* label,
+                    int label_dtype, int label_planes, long long label_stride, int H, int W, const int* rows, int n,
+                    long long* out, void* stream);
+
 /* PromptEncoder.mask_downscaling for mask prompts: masks fp32 [n,4g,4g] -> dense embeddings fp32 token-major [n,g*g,256].
  * wts = c1w[4][4] c1b[4] n1w[4] n1b[4] c2w[16][4][2][2] c2b[16] n2w[16] n2b[16] c3w[256][16] c3b[256] (4684 floats).
  * prompt_encoder.py:51-59,102-105; common.py:31-43 (LayerNorm2d) */

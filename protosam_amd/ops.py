@@ -1116,6 +1116,70 @@ def mask_binarize(low, idx, MID, H, W, variant, thr=0.0, label=None, out=None):
     return out, counts
 
 
+_SEG_DT = {torch.int16: 0, torch.float32: 1, torch.uint8: 2, torch.int32: 3}      # (slice_io._TORCH_DT: the codes of psam_volume_*)
+SEG_COLS = ("tp", "fp", "fn", "tn", "px0", "py0", "px1", "py1", "gx0", "gy0", "gx1", "gy1")
+
+
+def _seg_planes(t, name):
+    """t [planes, H, W] or [n, C, H, W] with contiguous [H, W] planes one stride apart -> (tensor to pass, planes, stride, H, W).
+    int64 is cast once on the device (to int32; label ids and {0, 1} masks fit)."""
+    if t.dim() not in (3, 4):
+        raise ValueError(f"{name}: expected [planes, H, W] or [n, C, H, W], got {tuple(t.shape)}")
+    if not t.is_cuda:
+        raise RuntimeError(f"{name}: expected a device tensor (protosam_amd has no CPU path)")
+    if t.dtype == torch.int64:
+        t = t.to(torch.int32)
+    if t.dtype not in _SEG_DT:
+        raise TypeError(f"{name}: expected one of {sorted(str(d) for d in _SEG_DT)} or int64, got {t.dtype}")
+    H, W = t.shape[-2:]
+    if H > 0 and W > 0 and (t.stride(-1) != 1 or t.stride(-2) != W):
+        t = t.contiguous()
+    if t.dim() == 4:
+        n, C = t.shape[:2]
+        if n > 1 and C > 1 and t.stride(0) != C * t.stride(1):      # planes are not evenly spaced
+            t = t.contiguous()
+        planes, stride = n * C, (t.stride(1) if C > 1 else t.stride(0))
+    else:
+        planes, stride = t.shape[0], t.stride(0)
+    return t, planes, stride, H, W
+
+
+def seg_counts(pred, label, rows, out=None):
+    """Confusion counts and boxes of many (prediction plane, label plane) pairs in one launch (psam_seg_counts).
+    pred / label: device tensors [planes, H, W] or [n, C, H, W] (planes numbered n-major) of int16 / float32 / uint8 / int32
+    (int64 is cast), same H, W; views with a storage offset or a plane stride are passed as they are.
+    rows: (pred plane, pred value, label plane, label value) per output row - a Python list / array (range-checked here, ValueError,
+    before anything touches the device) or an int32 device tensor [n, 4] (rows outside the planes are skipped by the kernel).
+    -> out int64 [n, 12], columns SEG_COLS; asynchronous on the current stream."""
+    if tuple(pred.shape[-2:]) != tuple(label.shape[-2:]):
+        raise ValueError(f"pred planes {tuple(pred.shape[-2:])} and label planes {tuple(label.shape[-2:])} differ")
+    if not isinstance(rows, torch.Tensor):
+        import numpy as np
+        r = np.asarray(rows, dtype=np.int64).reshape(-1, 4)
+        n_pred, n_lab = int(np.prod(pred.shape[:-2])), int(np.prod(label.shape[:-2]))
+        for k, (pp, _, lp, _) in enumerate(r.tolist()):
+            if not 0 <= pp < n_pred:
+                raise ValueError(f"rows[{k}]: prediction plane {pp} outside [0, {n_pred})")
+            if not 0 <= lp < n_lab:
+                raise ValueError(f"rows[{k}]: label plane {lp} outside [0, {n_lab})")
+        if r.size and (np.abs(r) > 0x7fffffff).any():
+            raise ValueError("rows: a value does not fit int32")
+        rows = torch.from_numpy(r.astype(np.int32)).to(pred.device)
+    pred, n_pred, s_pred, H, W = _seg_planes(pred, "pred")
+    label, n_lab, s_lab, _, _ = _seg_planes(label, "label")
+    _req(rows, torch.int32, "rows")
+    assert rows.is_contiguous() and rows.dim() == 2 and rows.shape[1] == 4
+    n = rows.shape[0]
+    if out is None:
+        out = torch.empty((n, 12), dtype=torch.int64, device=pred.device)
+    _req(out, torch.int64, "out")
+    assert out.is_contiguous() and out.numel() >= n * 12
+    st = _lib.lib().psam_seg_counts(_ptr(pred), _SEG_DT[pred.dtype], n_pred, s_pred, _ptr(label), _SEG_DT[label.dtype], n_lab, s_lab,
+                                   H, W, _ptr(rows), n, _ptr(out), _stream())
+    _lib.check(st, "psam_seg_counts")
+    return out
+
+
 def normalize_chw(x, mean3, std3, out=None):
     """(x - mean[c]) / std[c] on [B,3,H,W]; x uint8 or fp32."""
     import ctypes

@@ -11,6 +11,7 @@ import torch
 import torch.distributed as dist
 
 from .grid_proto_fewshot import FewShotSeg
+from .metrics import class_rows
 from .protosam import ALPNetWrapper, InputFactory, ProtoSAM, TYPE_ALPNET
 from .synth import synth_state_dict
 
@@ -57,14 +58,25 @@ def shard_slices(n_slices, rank, world):
     return list(range(rank, n_slices, world))
 
 
+def _batch_dst(out, buf, i, j):
+    """where the masks of slices i..j-1 go: their rows of the whole-run tensor `out`, or the front of the reused batch buffer"""
+    return out[i:j] if out is not None else buf[:j - i]
+
+
 @torch.no_grad()
 def run_slices(model, vol, sup_imgs, sup_masks, zs, device, out=None, batch=1, mix_parts=True):
     """Runs ProtoSAM on slices `zs` of `vol` [n,S,S] (device tensor), `batch` slices at a time through `forward_batch`; returns uint8
     masks [len(zs),S,S] and the number of prompts per slice. A batch may span z-parts (different support sets: the batch then carries
     one (input, count) pair per part - only the prototype match is done per part); mix_parts=False cuts batches at part boundaries."""
-    n, S = vol.shape[0], vol.shape[-1]
     if out is None:
-        out = torch.zeros((len(zs), S, S), dtype=torch.uint8, device=device)
+        out = torch.zeros((len(zs), vol.shape[-1], vol.shape[-1]), dtype=torch.uint8, device=device)
+    return out, _slices_loop(model, vol, sup_imgs, sup_masks, zs, device, out, None, batch, mix_parts, None)
+
+
+def _slices_loop(model, vol, sup_imgs, sup_masks, zs, device, out, buf, batch, mix_parts, sink):
+    """The loop of `run_slices`. The masks of a batch go to `out[i:j]`, or to the batch buffer `buf` when out is None;
+    sink(i, j, masks) is then called with them (`evaluate_slices` scores them there). -> prompts per slice."""
+    n, S = vol.shape[0], vol.shape[-1]
     stats = [0] * len(zs)
     inputs = {}
 
@@ -95,14 +107,17 @@ def run_slices(model, vol, sup_imgs, sup_masks, zs, device, out=None, batch=1, m
             cin = part_input(part, q) if len(runs) == 1 else [(part_input(pz, q), cnt) for pz, cnt in runs]
             res = model.forward_batch(q, cin)
             st = model.last_stats.get("per_slice", [model.last_stats])
+        dst = _batch_dst(out, buf, i, j)
         for k, (pred, scores) in enumerate(res):
             if pred.shape[-1] == S:
-                out[i + k].copy_(pred)            # ({0., 1.} -> uint8 inside the one copy kernel)
+                dst[k].copy_(pred)                # ({0., 1.} -> uint8 inside the one copy kernel)
             else:   # empty coarse mask: the reference hands back the all-zero 1024x1024 arg-max map (ProtoSAM.py:612-613)
-                out[i + k].zero_()
+                dst[k].zero_()
             stats[i + k] = st[k].get("n_prompts", 0) if k < len(st) else 0
+        if sink is not None:
+            sink(i, j, dst)
         i = j
-    return out, stats
+    return stats
 
 
 @torch.no_grad()
@@ -113,10 +128,24 @@ def run_slices_classes(model, vol, sup_imgs, sup_masks_per_part, zs, device, bat
     boundaries.
     Returns uint8 masks [len(zs), C, S, S] (the batch's output tensor is a slice of it) and the number of prompted classes per
     slice."""
-    n, S = vol.shape[0], vol.shape[-1]
-    C = len(sup_masks_per_part[0])
     if out is None:
-        out = torch.zeros((len(zs), C, S, S), dtype=torch.uint8, device=device)
+        out = torch.zeros((len(zs), len(sup_masks_per_part[0]), vol.shape[-1], vol.shape[-1]), dtype=torch.uint8, device=device)
+    return out, _slices_classes_loop(model, vol, sup_imgs, sup_masks_per_part, zs, device, batch, out, None, None)
+
+
+def _collect_classes(model, res, dst, stats, i):
+    """after a forward_classes_batch(out=dst) call on the slices from i on: the masks it did not write into dst, and the counts"""
+    for k, per_class in enumerate(res):
+        for c, (mask, _) in enumerate(per_class):
+            if mask.data_ptr() != dst[k, c].data_ptr():        # (an empty class: int64 zeros, and zeros in `dst` already)
+                dst[k, c].copy_(mask)
+    for (k, _) in model.last_stats.get("prompt", {}):          # (slice, class) pairs that went to the decoder
+        stats[i + k] += 1
+
+
+def _slices_classes_loop(model, vol, sup_imgs, sup_masks_per_part, zs, device, batch, out, buf, sink):
+    """The loop of `run_slices_classes`; out / buf / sink as `_slices_loop`."""
+    n, S = vol.shape[0], vol.shape[-1]
     stats = [0] * len(zs)
     i = 0
     while i < len(zs):
@@ -126,16 +155,13 @@ def run_slices_classes(model, vol, sup_imgs, sup_masks_per_part, zs, device, bat
             j += 1
         idx = torch.tensor(zs[i:j], device=device)
         q = vol[idx][:, None].expand(j - i, 3, S, S).contiguous()
-        dst = out[i:j]
+        dst = _batch_dst(out, buf, i, j)
         res = model.forward_classes_batch(q, sup_imgs[part], sup_masks_per_part[part], out=dst)
-        for k, per_class in enumerate(res):
-            for c, (mask, _) in enumerate(per_class):
-                if mask.data_ptr() != dst[k, c].data_ptr():        # (an empty class: int64 zeros, and zeros in `dst` already)
-                    dst[k, c].copy_(mask)
-        for (k, _) in model.last_stats.get("prompt", {}):          # (slice, class) pairs that went to the decoder
-            stats[i + k] += 1
+        _collect_classes(model, res, dst, stats, i)
+        if sink is not None:
+            sink(i, j, dst)
         i = j
-    return out, stats
+    return stats
 
 
 def _class_zlists(label_vol, classes):
@@ -208,25 +234,82 @@ def run_slices_class_supports(model, vol, supports, part_table, zs, batch=16, ou
     (`class_part_table`). `batch` consecutive slices go to one `model.forward_classes_batch(..., supports=...)` call whatever
     their parts: each class's runs of equal part become its (input, n) list.
     Returns uint8 masks [len(zs), C, S, S] and the number of prompted classes per slice, as `run_slices_classes`."""
-    S, dev = vol.shape[-1], vol.device
-    C = len(supports)
     if out is None:
-        out = torch.zeros((len(zs), C, S, S), dtype=torch.uint8, device=dev)
+        out = torch.zeros((len(zs), len(supports), vol.shape[-1], vol.shape[-1]), dtype=torch.uint8, device=vol.device)
+    return out, _slices_class_supports_loop(model, vol, supports, part_table, zs, batch, out, None, None)
+
+
+def _slices_class_supports_loop(model, vol, supports, part_table, zs, batch, out, buf, sink):
+    """The loop of `run_slices_class_supports`; out / buf / sink as `_slices_loop`."""
+    S, dev = vol.shape[-1], vol.device
     stats = [0] * len(zs)
     for i in range(0, len(zs), batch):
         zb = list(zs[i:i + batch])
         idx = torch.tensor(zb, device=dev)
         q = vol[idx][:, None].expand(len(zb), 3, S, S).contiguous()
         specs = class_support_specs(supports, part_table, zb)
-        dst = out[i:i + len(zb)]
+        dst = _batch_dst(out, buf, i, i + len(zb))
         res = model.forward_classes_batch(q, supports=specs, out=dst)
-        for k, per_class in enumerate(res):
-            for c, (mask, _) in enumerate(per_class):
-                if mask.data_ptr() != dst[k, c].data_ptr():        # (an empty class: int64 zeros, and zeros in `dst` already)
-                    dst[k, c].copy_(mask)
-        for (k, _) in model.last_stats.get("prompt", {}):          # (slice, class) pairs that went to the decoder
-            stats[i + k] += 1
-    return out, stats
+        _collect_classes(model, res, dst, stats, i)
+        if sink is not None:
+            sink(i, i + len(zb), dst)
+    return stats
+
+
+# ---- evaluation: score every batch where it lies; only a [rows, 12] table is kept (DESIGN.md section 4b) --------------------------
+def _scoring(labels, zs, classes, keep, batch, shape, device, label_value=1):
+    """table, batch buffer and sink of the evaluate_* functions. shape: of one slice's masks ([C, S, S] or [S, S])."""
+    from . import ops
+    per = 1 if classes is None else len(classes)
+    table = torch.empty((len(zs) * per, 12), dtype=torch.int64, device=device)
+    if keep is not None:
+        assert tuple(keep.shape) == (len(zs),) + tuple(shape) and keep.dtype == torch.uint8 and keep.is_contiguous()
+    buf = None if keep is not None else torch.empty((min(batch, len(zs)),) + tuple(shape), dtype=torch.uint8, device=device)
+
+    def sink(i, j, masks):
+        rows = class_rows(j - i, classes, label_planes=zs[i:j], label_value=label_value)
+        ops.seg_counts(masks, labels, rows.tolist(), out=table[i * per:j * per])
+    return table, buf, sink
+
+
+@torch.no_grad()
+def evaluate_slices(model, vol, labels, sup_imgs, sup_masks, zs, device, batch=1, mix_parts=True, keep=None, label_value=1):
+    """`run_slices` scored in place: the masks of each batch go to ONE reused batch-sized buffer and one `ops.seg_counts` compares
+    them with `labels` [Z, S, S] (the scan's label volume on the device, true where == label_value). Returns the int64 table
+    [len(zs), 12] (ops.SEG_COLS; still on the device, nothing synchronised) and the prompts per slice. keep= (uint8
+    [len(zs), S, S]) also receives the masks, as `run_slices(..., out=keep)`."""
+    S = vol.shape[-1]
+    table, buf, sink = _scoring(labels, list(zs), None, keep, batch, (S, S), device, label_value)
+    return table, _slices_loop(model, vol, sup_imgs, sup_masks, zs, device, keep, buf, batch, mix_parts, sink)
+
+
+@torch.no_grad()
+def evaluate_slices_classes(model, vol, labels, sup_imgs, sup_masks_per_part, zs, classes, device, batch=16, keep=None):
+    """`run_slices_classes` scored in place against the label volume `labels` [Z, S, S]: class c of the call is organ classes[c].
+    One reused [batch, C, S, S] buffer, one `ops.seg_counts` per model call. Returns the int64 table [len(zs) * C, 12] (row
+    k * C + c = slice zs[k], class c; on the device) and the prompted classes per slice. keep= (uint8 [len(zs), C, S, S]) also
+    receives the masks."""
+    S, C = vol.shape[-1], len(classes)
+    assert C == len(sup_masks_per_part[0])
+    table, buf, sink = _scoring(labels, list(zs), classes, keep, batch, (C, S, S), device)
+    return table, _slices_classes_loop(model, vol, sup_imgs, sup_masks_per_part, zs, device, batch, keep, buf, sink)
+
+
+@torch.no_grad()
+def evaluate_slices_class_supports(model, vol, labels, supports, part_table, zs, classes, batch=16, keep=None):
+    """`run_slices_class_supports` scored in place; table, counts and keep= as `evaluate_slices_classes`."""
+    S, C = vol.shape[-1], len(classes)
+    assert C == len(supports)
+    table, buf, sink = _scoring(labels, list(zs), classes, keep, batch, (C, S, S), vol.device)
+    return table, _slices_class_supports_loop(model, vol, supports, part_table, zs, batch, keep, buf, sink)
+
+
+def gather_counts(local, world):
+    """One all-gather of the per-rank int64 counts tables [k, 12] -> [world*k, 12] (rank-major; `interleave_rank_major` puts the
+    rows back in z order): 96 bytes per (slice, class) cross the link instead of an S*S mask."""
+    if world == 1 or not dist.is_initialized():
+        return local
+    return all_gather_rows(local)
 
 
 def gather_masks(local, world):
