@@ -101,6 +101,8 @@ int psam_layernorm(const float* x, const float* w, const float* b, void* y, floa
  * pack: the query-side terms are then computed inside the kernel and never touch HBM).
  * mode 1 with rel_h = rel_w = null and rpack = psam_relpos' GLOBAL table pack: the decomposed rel-pos terms are computed inside the
  * assembly kernel (psam_gattn_asm_{80,64}_fused) for the shapes psam_attention_fused_relpos reports; PSAM_ERR_ARG elsewhere.
+ * mode 1 with gw != 64: any gh x gw token map with 1 <= gh, gw <= 64 (N = gh * gw; SAM encoders built for 256 / 384 / 512 pixel inputs)
+ * from `rpack` alone (rel_h = rel_w = null): gattn_any_kernel computes the terms itself, both qkv layouts; larger maps PSAM_ERR_ARG.
  * mode 0 with hd = 64 and N >= 128 (DINOv2 at 1297 / 5330 tokens) runs the assembly kernel psam_gattn_asm_64_norel: any token count,
  * the last key tile masked; models/grid_proto_fewshot.py:88-98 (the hub model's Attention.forward).
  * head_major = 0: qkv is token-major [B,N,3,H,hd]; 1: head-major [3,H,B*N,hd] as written by psam_gemm_f16_heads.
@@ -112,7 +114,7 @@ int psam_attention_f16(const void* qkv, void* out, const float* rel_h, const flo
  * form); bits 1-2: window kernel (0 attn_kernel, 1 wattn_kernel, 2 the assembly kernel of csrc/wattn_asm_gen.py where it applies -
  * rpack given, hd = 80, 14 x 14 windows of a 64 x 64 token map, token-major qkv - and the persistent wattn_p_kernel elsewhere, 3
  * wattn_p_kernel everywhere); bit 3: the register-staged HIP
- * global kernel; bit 4: the DMA-fed HIP global kernel everywhere; neither bit 3 nor 4: the assembly global kernel
+ * global kernel; bit 5: mode 1 with `rpack` alone runs the any-map kernel at gw == 64 too (tests, A/B); bit 4: the DMA-fed HIP global kernel everywhere; neither bit 3 nor 4: the assembly global kernel
  * (csrc/gattn_asm_gen.py) where it applies - rel-pos: hd = 80 or 64, N a multiple of 256; no bias: hd = 64, N >= 128; any head count
  * and batch - and the DMA-fed HIP kernel elsewhere. */
 int psam_attention_set_variant(int v);

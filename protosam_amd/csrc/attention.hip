@@ -1615,13 +1615,314 @@ __global__ __launch_bounds__(256, 2) void gattn_kernel(AttnArgs p) {
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Global attention with decomposed rel-pos for ANY gh x gw token map, 1 <= gh, gw <= 64 (`gattn_any_kernel`; mode 1 with gw != 64):
+// gattn_kernel's tile loop (DMA-fed double-buffered 64-key tiles, V2 softmax, row sums on the matrix pipe) with the two things that
+// kernel takes from "a 64-key tile is one key row" made general:
+//   * the rel-pos terms are computed in the kernel from the packed tables (`rpack`, global form: [2][2][128][HDP], hi / lo halves):
+//     per wave and query tile T[r][q] = q . R[r] for the 2K - 1 rows of both tables as MFMAs (table fragment = A, the query
+//     fragments already in registers = B), scattered as rel[q][k = pos(q) - r + K - 1] * log2(e) into two fp32 LDS stages
+//     [128 queries][RL + 1] (RL = 32 when both sides of the map are <= 32, else 64; the odd row stride spreads the 16 query rows
+//     of a read over the banks). No psam_relpos launch, no fp32 [B,H,N,64] x 2 round trip;
+//   * a key tile may straddle rows of the map: the tile's first key (kh0, kw0) is carried as a wave-uniform pair, a lane's two
+//     runs of eight consecutive keys start at (kh0 + d, x - d gw) with x = kw0 + run offset < 128 and d = x / gw by multiply-shift,
+//     and step through the row ends; each score takes rel_h[q][kh] + rel_w[q][kw] from the stages.
+// Keys >= N of the last tile (N % 64 != 0) are set to -inf BEFORE the running max; their K / V rows are clamped copies of key N - 1
+// (finite), their stage indices clamped into the row.
+template <int HD, int RL, bool FULL>
+// (RL = 64: 105 KB of LDS, one workgroup per CU - the register budget follows)
+__global__ __launch_bounds__(256, (RL == 32 ? 2 : 1)) void gattn_any_kernel(AttnArgs p) {
+  constexpr int NW = 4, NT = 256, QB = 128;
+  constexpr int HDP = (HD + 31) / 32 * 32;
+  constexpr int KS = HDP / 32;
+  constexpr int DT = HD / 16;
+  constexpr int CH = HD / 8;
+  constexpr int RC = 10, RLD = RC * 8;
+  constexpr int IMG = KT * RLD;
+  constexpr int NINS = (KT * RC) / 64;
+  constexpr int NDMA = (NINS + NW - 1) / NW;
+  constexpr int RLP = RL + 1;                          // stage row stride (floats)
+  constexpr int RP = 128;                              // table rows of the global pack
+  const float LOG2E = 1.4426950408889634f;
+  const float RESCALE_THR = 8.0f;
+
+  __shared__ __attribute__((aligned(16))) half_t Kb[2 * IMG];
+  __shared__ __attribute__((aligned(16))) half_t Vb[2 * IMG];
+  __shared__ float relh_s[QB * RLP];                   // rel_h[q][kh] * log2(e)
+  __shared__ float relw_s[QB * RLP];                   // rel_w[q][kw] * log2(e)
+
+  const int t = threadIdx.x;
+  const int lane = t & 63, wv = __builtin_amdgcn_readfirstlane(t >> 6);
+  const int li = lane & 15, g = lane >> 4;
+  (void)NT;
+  int h, b, qblk;
+  {
+    const int per = p.nqb, nshare = p.B * p.H;
+    const int gq = blockIdx.x / (8 * per), r = blockIdx.x % (8 * per);
+    const int grp = gq * 8 + (r & 7);
+    if (grp >= nshare) return;
+    qblk = r >> 3;
+    h = grp % p.H;
+    b = grp / p.H;
+  }
+  const int N = p.N, H = p.H, gh = p.gh, gw = p.gw;
+  const size_t rs = (size_t)p.ts;
+  const half_t* qkv_b = p.qkv + (size_t)b * N * rs;
+  const int ntiles = (N + KT - 1) / KT;
+
+  int dkey[2][NDMA], dchunk[NDMA];
+#pragma unroll
+  for (int i = 0; i < NDMA; ++i) {
+    const int S = (wv + i * NW) * 64 + lane;
+    const int R = S / RC, c = S - R * RC;
+    const int rho = R & 31, C = R >> 5;
+    dkey[0][i] = C * 32 + ((rho >> 2) & 3) * 8 + (rho >> 4) * 4 + (rho & 3);
+    dkey[1][i] = C * 32 + ((rho >> 4) * 2 + ((rho >> 2) & 1)) * 8 + ((rho >> 3) & 1) * 4 + (rho & 3);
+    dchunk[i] = c;
+  }
+  const half_t* kbase = qkv_b + (size_t)p.ws_ + (size_t)h * p.hs;
+  const half_t* vbase = qkv_b + 2 * (size_t)p.ws_ + (size_t)h * p.hs;
+  auto dma_tile = [&](int tile, int buf) {
+#pragma unroll
+    for (int i = 0; i < NDMA; ++i) {
+      if (wv + i * NW < NINS) {
+        int kk = tile * KT + dkey[0][i], kv = tile * KT + dkey[1][i];
+        if (!FULL) { kk = kk < N ? kk : N - 1; kv = kv < N ? kv : N - 1; }
+        if (dchunk[i] < CH) {
+          __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(kbase + (size_t)kk * rs + dchunk[i] * 8),
+                                           (__attribute__((address_space(3))) void*)(Kb + buf * IMG + (wv + i * NW) * 512), 16, 0, 0);
+          __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(vbase + (size_t)kv * rs + dchunk[i] * 8),
+                                           (__attribute__((address_space(3))) void*)(Vb + buf * IMG + (wv + i * NW) * 512), 16, 0, 0);
+        }
+      }
+    }
+  };
+  dma_tile(0, 0);
+
+  // ---- query fragments ---------------------------------------------------------------------------------
+  const int qrow_blk = qblk * QB + wv * 32;
+  int qtok[2];
+  bool qvalid[2];
+  half8_t qf[2][KS];
+#pragma unroll
+  for (int qt = 0; qt < 2; ++qt) {
+    const int q = qrow_blk + qt * 16 + li;
+    qvalid[qt] = q < N;
+    qtok[qt] = q < N ? q : 0;
+    const half_t* qp = qkv_b + (size_t)qtok[qt] * rs + (size_t)h * p.hs;
+#pragma unroll
+    for (int s = 0; s < KS; ++s) {
+      const int c0 = s * 32 + g * 8;
+      if (c0 < HD) {
+        qf[qt][s] = *reinterpret_cast<const half8_t*>(qp + c0);
+      } else {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) qf[qt][s][e] = (half_t)0.f;
+      }
+    }
+  }
+
+  // ---- rel-pos stages (add_decomposed_rel_pos, image_encoder.py:337-372, from the UNSCALED q) --------------------------------
+  // each wave fills the rows of its own 32 queries; every (q, k < K) is written exactly once (r = pos - k + K - 1 runs over
+  // 0 .. 2K - 2, all inside the ceil((2K - 1) / 16) row tiles walked)
+  {
+    int qy[2], qx[2];
+#pragma unroll
+    for (int qt = 0; qt < 2; ++qt) {
+      qy[qt] = qtok[qt] / gw;
+      qx[qt] = qtok[qt] - qy[qt] * gw;
+    }
+#pragma unroll 1
+    for (int tab = 0; tab < 2; ++tab) {
+      const int K = tab ? gw : gh;
+      const int nrt = (2 * K - 1 + 15) >> 4;                 // <= 8: rows < 128 = RP
+      const half_t* Rhi = p.rpack + (size_t)(tab * 2 + 0) * RP * HDP;
+      const half_t* Rlo = p.rpack + (size_t)(tab * 2 + 1) * RP * HDP;
+      float* stage = tab ? relw_s : relh_s;
+#pragma unroll 1
+      for (int rt = 0; rt < nrt; ++rt) {
+        half8_t rh[KS], rl[KS];
+#pragma unroll
+        for (int s = 0; s < KS; ++s) {
+          const size_t off = (size_t)(rt * 16 + li) * HDP + s * 32 + g * 8;
+          rh[s] = *reinterpret_cast<const half8_t*>(Rhi + off);
+          rl[s] = *reinterpret_cast<const half8_t*>(Rlo + off);
+        }
+#pragma unroll
+        for (int qt = 0; qt < 2; ++qt) {
+          f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+          for (int s = 0; s < KS; ++s) {
+            acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(rh[s], qf[qt][s], acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(rl[s], qf[qt][s], acc, 0, 0, 0);
+          }
+          // lane (li, g): query li of the tile against table rows r0 .. r0 + 3 = keys k0, k0 - 1, k0 - 2, k0 - 3
+          const int k0 = (tab ? qx[qt] : qy[qt]) - (rt * 16 + g * 4) + K - 1;
+          float* row = stage + (wv * 32 + qt * 16 + li) * RLP;
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const int kk = k0 - e;
+            if (kk >= 0 && kk < K) row[kk] = acc[e] * LOG2E;
+          }
+        }
+      }
+    }
+  }
+
+  f32x4 ot[DT][2];
+#pragma unroll
+  for (int d = 0; d < DT; ++d)
+#pragma unroll
+    for (int qt = 0; qt < 2; ++qt) ot[d][qt] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const float sl2 = p.scale * LOG2E;
+  float mrun[2] = {-INFINITY, -INFINITY};
+  f32x4 lt[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
+  half8_t ones;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) ones[e] = (half_t)1.f;
+  const int gwm = (65536 + gw - 1) / gw;      // x / gw = (x * gwm) >> 16 for x < 128, gw <= 64 (error < 128 / 65536 < 1 / gw)
+  const int step_h = KT / gw, step_w = KT - step_h * gw;   // a tile advances the first key by 64 = step_h rows + step_w columns
+  int kh0 = 0, kw0 = 0;                       // (row, column) of the tile's first key: wave-uniform
+  const int rq[2] = {(wv * 32 + li) * RLP, (wv * 32 + 16 + li) * RLP};   // the lane's two stage rows
+
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();   // tile 0 and the stages are in
+
+#pragma unroll 1
+  for (int tile = 0; tile < ntiles; ++tile) {
+    const int buf = tile & 1;
+    if (tile + 1 < ntiles) dma_tile(tile + 1, buf ^ 1);
+    const half_t* Ks = Kb + buf * IMG;
+    const half_t* Vs = Vb + buf * IMG;
+    const int kbase_i = tile * KT;
+    const bool last_partial = !FULL && (tile == ntiles - 1) && (N % KT != 0);
+    f32x4 st[4][2];
+#pragma unroll
+    for (int tt = 0; tt < 4; ++tt) {
+#pragma unroll
+      for (int qt = 0; qt < 2; ++qt) st[tt][qt] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int s = 0; s < KS; ++s) {
+        const int kc = (s * 4 + 3 < CH) ? s * 4 + g : min(s * 4 + g, CH - 1);
+        const half8_t kf = *reinterpret_cast<const half8_t*>(&Ks[(tt * 16 + li) * RLD + kc * 8]);
+#pragma unroll
+        for (int qt = 0; qt < 2; ++qt) st[tt][qt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf, qf[qt][s], st[tt][qt], 0, 0, 0);
+      }
+    }
+    // scale + rel_h[q][kh] + rel_w[q][kw] (+ mask): the lane's keys are two runs of eight, key = kbase + half * 32 + g * 8 + j,
+    // held as st[half * 2 + (j >> 2)][.][j & 3]
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+      const int x = kw0 + half * 32 + g * 8;
+      const int d = (x * gwm) >> 16;
+      int kh = kh0 + d, kw = x - d * gw;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const int tt = half * 2 + (j >> 2), r = j & 3;
+        const int khc = FULL ? kh : min(kh, RL - 1);
+#pragma unroll
+        for (int qt = 0; qt < 2; ++qt) {
+          float sv = fmaf(st[tt][qt][r], sl2, relh_s[rq[qt] + khc] + relw_s[rq[qt] + kw]);
+          if (!FULL && last_partial) {
+            if (kbase_i + half * 32 + g * 8 + j >= N) sv = -INFINITY;
+          }
+          st[tt][qt][r] = sv;
+        }
+        ++kw;
+        if (kw == gw) { kw = 0; ++kh; }
+      }
+    }
+    kh0 += step_h;
+    kw0 += step_w;
+    if (kw0 >= gw) { kw0 -= gw; ++kh0; }
+    half8_t pf[2][2];
+    {
+      float mx[2];
+#pragma unroll
+      for (int qt = 0; qt < 2; ++qt) {
+        float mt[4];
+#pragma unroll
+        for (int tt = 0; tt < 4; ++tt)
+          mt[tt] = fmaxf(fmaxf(st[tt][qt][0], st[tt][qt][1]), fmaxf(st[tt][qt][2], st[tt][qt][3]));
+        mx[qt] = fmaxf(fmaxf(mt[0], mt[1]), fmaxf(mt[2], mt[3]));
+      }
+#pragma unroll
+      for (int qt = 0; qt < 2; ++qt) {
+        mx[qt] = fmaxf(mx[qt], __shfl_xor(mx[qt], 16, 64));
+        mx[qt] = fmaxf(mx[qt], __shfl_xor(mx[qt], 32, 64));
+      }
+      if (!__all(mx[0] <= mrun[0] + RESCALE_THR && mx[1] <= mrun[1] + RESCALE_THR)) {
+#pragma unroll
+        for (int qt = 0; qt < 2; ++qt) {
+          const float mnew = fmaxf(mrun[qt], mx[qt]);
+          const float alpha = __builtin_amdgcn_exp2f(mrun[qt] - mnew);
+          mrun[qt] = mnew;
+#pragma unroll
+          for (int r = 0; r < 4; ++r) lt[qt][r] *= alpha;
+#pragma unroll
+          for (int d = 0; d < DT; ++d)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) ot[d][qt][r] *= alpha;
+        }
+      }
+#pragma unroll
+      for (int qt = 0; qt < 2; ++qt)
+#pragma unroll
+        for (int tt = 0; tt < 4; ++tt)
+#pragma unroll
+          for (int r = 0; r < 4; ++r)
+            pf[qt][tt >> 1][(tt & 1) * 4 + r] = (half_t)__builtin_amdgcn_exp2f(st[tt][qt][r] - mrun[qt]);
+    }
+#pragma unroll
+    for (int s2 = 0; s2 < 2; ++s2)
+#pragma unroll
+      for (int qt = 0; qt < 2; ++qt) lt[qt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ones, pf[qt][s2], lt[qt], 0, 0, 0);
+#pragma unroll
+    for (int s2 = 0; s2 < 2; ++s2) {
+      const int vrow = s2 * 32 + (g >> 1) * 16 + (g & 1) * 4 + (li >> 2);
+      const half_t* vb = &Vs[vrow * RLD + (li & 3) * 4];
+#pragma unroll
+      for (int d = 0; d < DT; ++d) {
+        const fp16x4_t v0 = __builtin_amdgcn_ds_read_tr16_b64_v4f16((__attribute__((address_space(3))) fp16x4_t*)(vb + d * 16));
+        const fp16x4_t v1 = __builtin_amdgcn_ds_read_tr16_b64_v4f16((__attribute__((address_space(3))) fp16x4_t*)(vb + d * 16 + 8 * RLD));
+        half8_t vf;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          vf[e] = (half_t)v0[e];
+          vf[4 + e] = (half_t)v1[e];
+        }
+#pragma unroll
+        for (int qt = 0; qt < 2; ++qt) ot[d][qt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vf, pf[qt][s2], ot[d][qt], 0, 0, 0);
+      }
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+  }
+
+#pragma unroll
+  for (int qt = 0; qt < 2; ++qt) {
+    const float inv = 1.0f / lt[qt][0];
+    if (qvalid[qt]) {
+      half_t* op = p.out + ((size_t)b * N + qtok[qt]) * ((size_t)H * HD) + (size_t)h * HD;
+#pragma unroll
+      for (int d = 0; d < DT; ++d) {
+        half4_t o = {(half_t)(ot[d][qt][0] * inv), (half_t)(ot[d][qt][1] * inv), (half_t)(ot[d][qt][2] * inv),
+                     (half_t)(ot[d][qt][3] * inv)};
+        *reinterpret_cast<half4_t*>(op + d * 16 + g * 4) = o;
+      }
+    }
+  }
+}
+
 static int g_attn_v2 = -1;
+static int g_gattn_any = 0;   // 1: gattn_any_kernel also at gw == 64 when only the packed tables are given (tests, A/B)
 static int g_gattn = -1;   // 1: gattn_kernel for modes 0 / 1
 static int g_wattn = -1;   // 1: wattn_kernel for mode 2 (needs rpack with the appended tables), 0: attn_kernel<HD, 2, 7>
 extern "C" int psam_attention_set_variant(int v) {   // bit 0: V2 softmax in the global kernels (0 = round 1's serial chains); bit 1: wattn_kernel
   g_attn_v2 = (v & 1) ? 1 : 0;                        // for the windows. Default 5; A/B and tests
   g_gattn = (v & 8) ? 0 : (v & 16) ? 1 : 3;            // bit 3: the register-staged global kernel (attn_kernel); bit 4: gattn_kernel (HIP, DMA-fed)
                                                       // everywhere; neither: the assembly kernel (gattn_asm_gen.py) where it applies
+  g_gattn_any = (v & 32) ? 1 : 0;                     // bit 5: mode 1 with only `rpack` given runs gattn_any_kernel at gw == 64 too
   g_wattn = (v >> 1) & 3;                             // bits 1-2: 0 attn_kernel<HD, 2, 7>, 1 wattn_kernel, 2 the assembly kernel where it
                                                       // applies (else wattn_p_kernel), 3 wattn_p_kernel everywhere
   return PSAM_OK;
@@ -1846,6 +2147,19 @@ static int launch_attn(AttnArgs p, int mode, hipStream_t s) {
     dim3 grid(groups8 * 8 * p.nqb), block(NW * 64);
     const bool full = (p.N % 64) == 0;
     if (g_gattn < 0) { const char* e = getenv("PSAM_GATTN"); g_gattn = e ? atoi(e) : 3; }   // 3: the assembly kernel where it applies, else gattn_kernel
+    if (mode == 1 && p.rpack && (!p.rel_h || !p.rel_w) && (p.gw != KT || g_gattn_any)) {
+      // any gh x gw map up to 64 x 64 from the packed tables alone (the host entry checked the sizes): gattn_any_kernel
+      if (p.gh > KT || p.gw > KT) return PSAM_ERR_ARG;
+      const bool small = p.gh <= 32 && p.gw <= 32;     // stage rows of 32 floats: 74 KB of LDS, two workgroups per CU
+      if (small) {
+        if (full) hipLaunchKernelGGL((gattn_any_kernel<HD, 32, true>), grid, block, 0, s, p);
+        else hipLaunchKernelGGL((gattn_any_kernel<HD, 32, false>), grid, block, 0, s, p);
+      } else {
+        if (full) hipLaunchKernelGGL((gattn_any_kernel<HD, 64, true>), grid, block, 0, s, p);
+        else hipLaunchKernelGGL((gattn_any_kernel<HD, 64, false>), grid, block, 0, s, p);
+      }
+      return psam_launch_status();
+    }
     if (mode == 1 && (!p.rel_h || !p.rel_w)) {      // tables only: the fused kernel or nothing (psam_attention_fused_relpos tells the caller)
       if (p.rpack && gattn_asm_eligible(p, mode, HD, 1)) return launch_gattn_asm(p, s, HD, 1);
       return PSAM_ERR_ARG;
@@ -1873,7 +2187,7 @@ static int launch_attn(AttnArgs p, int mode, hipStream_t s) {
   return psam_launch_status();
 }
 
-// mode 0: global, no bias.  mode 1: global + decomposed rel-pos (requires gw == 64, N == gh*gw).
+// mode 0: global, no bias.  mode 1: global + decomposed rel-pos (N == gh*gw; gw == 64, or any gh, gw <= 64 with `rpack` alone).
 // mode 2: ws x ws windows over the gh x gw token map (zero-padded as the reference) + rel-pos folded into the MFMA
 //         (relq = psam_relpos' windowed output).
 extern "C" int psam_attention_f16(const void* qkv, void* out, const float* rel_h, const float* rel_w,
@@ -1903,7 +2217,10 @@ extern "C" int psam_attention_f16(const void* qkv, void* out, const float* rel_h
   p.nwx = p.nwin = 0;
   { const char* e = getenv("PSAM_ATTN_DBG"); p.dbg = e ? atoi(e) : 0; }
   if (mode == 1) {   // rel_h / rel_w from psam_relpos, or the packed tables alone (the rel-pos terms are then computed in the kernel)
-    if (gw != KT || gh * gw != N || ((!rel_h || !rel_w) && !rpack)) return PSAM_ERR_ARG;
+    // gw == 64: the kernels whose key tile is one row of the map. Any other gh x gw up to 64 x 64: gattn_any_kernel, which needs the
+    // packed tables (it computes the terms itself)
+    if (gh * gw != N || ((!rel_h || !rel_w) && !rpack)) return PSAM_ERR_ARG;
+    if (gw != KT && (gh < 1 || gw < 1 || gh > KT || gw > KT || !rpack || rel_h || rel_w)) return PSAM_ERR_ARG;
   }
   if (mode == 2) {
     // the resident-window schedule is laid out for 14 x 14 = 3 x 64 + 4 keys (SAM's window_size, build_sam.py:73)

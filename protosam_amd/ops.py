@@ -400,7 +400,9 @@ def layernorm(x, weight, bias, eps, out=None, out_dtype=torch.float16, out2=None
 def attention(qkv, B, N, H, hd, scale, out=None, mode=0, rel_h=None, rel_w=None, relq=None, pad_row=None, gh=0, gw=0,
               ws=0, head_major=False, rpack=None):
     """qkv fp16 [B,N,3,H,hd] (packed as nn.Linear(dim,3*dim) emits it) or, head_major, [3,H,B*N,hd] (gemm_heads)
-    -> fp16 [B,N,H*hd]."""
+    -> fp16 [B,N,H*hd]. mode 1 (global + decomposed rel-pos) on a gh x gw token map: gw == 64 with rel_h / rel_w from `relpos` (or
+    `rpack` alone where `attention_fused_relpos` says so); any other map with 1 <= gh, gw <= 64 with `rpack` alone
+    (`pack_rel_tables`, global form) - the kernel computes the terms itself, both layouts."""
     _req(qkv, torch.float16, "qkv"); _req(rel_h, torch.float32, "rel_h"); _req(rel_w, torch.float32, "rel_w")
     _req(pad_row, torch.float16, "pad_row"); _req(relq, torch.float16, "relq"); _req(rpack, torch.float16, "rpack")
     assert qkv.is_contiguous()
@@ -436,7 +438,8 @@ def attention_fused_relpos(B, N, H, hd, gh, gw):
 def attention_set_variant(v):
     """bit 0: V2 softmax in the global kernels (0 = round-1 serial form); bits 1-2: window kernel of the fused rel-pos path
     (0 attn_kernel, 1 wattn_kernel, 2 the persistent wattn_p_kernel); bit 3: the register-staged HIP global kernel; bit 4: the
-    DMA-fed HIP global kernel everywhere (neither: the assembly global kernel where it applies, see include/protosam_hip.h).
+    DMA-fed HIP global kernel everywhere (neither: the assembly global kernel where it applies, see include/protosam_hip.h); bit 5:
+    mode 1 with `rpack` alone runs the any-map kernel at gw == 64 too.
     Default 5; for A/B and the equivalence tests."""
     _bump_dispatch()
     _lib.check(_lib.lib().psam_attention_set_variant(int(v)), "psam_attention_set_variant")

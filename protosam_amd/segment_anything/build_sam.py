@@ -26,9 +26,11 @@ sam_model_registry = {"default": build_sam_vit_h, "vit_h": build_sam_vit_h, "vit
 
 
 def _build_sam(encoder_embed_dim, full_depth, encoder_num_heads, encoder_global_attn_indexes, checkpoint=None,
-               encoder_depth=None):
-    """encoder_depth (test hook): truncate the block stack; only meaningful with random-weight fixtures."""
-    prompt_embed_dim, image_size, vit_patch_size = 256, 1024, 16
+               encoder_depth=None, image_size=1024):
+    """encoder_depth (test hook): truncate the block stack; only meaningful with random-weight fixtures.
+    image_size: the model's own input side, a multiple of 16 up to 1024 (token maps up to 64 x 64). A checkpoint must have been
+    trained at that size: `pos_embed` and the global blocks' rel-pos tables differ in shape, and nothing is interpolated here."""
+    prompt_embed_dim, vit_patch_size = 256, 16
     image_embedding_size = image_size // vit_patch_size
     depth = full_depth if encoder_depth is None else encoder_depth
     sam = Sam(

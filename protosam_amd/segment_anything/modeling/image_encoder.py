@@ -69,6 +69,8 @@ class Attention(nn.Module):
             relq = ops.relpos(qkv, rpack, B, N, H, hd, g, ws, True, self.scale, relq=relq, head_major=hm)
             return ops.attention(qkv, B, N, H, hd, self.scale, out=out, mode=2, relq=relq, pad_row=pad_row, gh=g, gw=g, ws=ws,
                                  head_major=hm)
+        if g != 64:   # any map up to 64 x 64: the kernel computes the rel-pos terms itself from the packed tables (gattn_any_kernel)
+            return ops.attention(qkv, B, N, H, hd, self.scale, out=out, mode=1, rpack=rpack, gh=g, gw=g, head_major=hm)
         if ops.attention_fused_relpos(B, N, H, hd, g, g):   # rel_h / rel_w computed inside the attention kernel (round 5)
             return ops.attention(qkv, B, N, H, hd, self.scale, out=out, mode=1, rpack=rpack, gh=g, gw=g)
         relh, relw = rel_bufs() if rel_bufs is not None else (None, None)
@@ -77,13 +79,15 @@ class Attention(nn.Module):
 
     @torch.no_grad()
     def forward(self, x):
-        """image_encoder.py:235-251 for the map a GLOBAL block hands over: x [B,64,64,dim] -> [B,64,64,dim] fp32 (qkv GEMM, fused
-        attention with the decomposed rel-pos of `rel_pos_h / rel_pos_w`, proj GEMM). The 14 x 14 windows of a windowed block never
-        exist as tensors here (`Block.forward` runs them as index math inside the kernel), so a [B*nW,14,14,dim] input has no kernel."""
+        """image_encoder.py:235-251 for the map a GLOBAL block hands over: x [B,g,g,dim] -> [B,g,g,dim] fp32, g <= 64 the side the
+        module's own `rel_pos_h / rel_pos_w` were built for (2g - 1 rows): qkv GEMM, fused attention with the decomposed rel-pos, proj
+        GEMM. The 14 x 14 windows of a windowed block never exist as tensors here (`Block.forward` runs them as index math inside the
+        kernel), so a [B*nW,14,14,dim] input has no kernel."""
         B, gh, gw, D = x.shape
-        if not self.use_rel_pos or gh != gw or gh != 64 or self.rel_pos_h.shape[0] != 2 * gh - 1:
-            raise NotImplementedError("Attention.forward: the 64 x 64 token map of a global block with its 127-row rel-pos tables; "
-                                      "windowed blocks run through Block.forward")
+        if (not self.use_rel_pos or gh != gw or gh > 64 or self.rel_pos_h.shape[0] != 2 * gh - 1
+                or self.rel_pos_w.shape[0] != 2 * gw - 1):
+            raise NotImplementedError("Attention.forward: the square g x g token map (g <= 64) of a global block whose rel-pos tables "
+                                      "have 2g - 1 rows; windowed blocks run through Block.forward")
         x16 = x.reshape(B * gh * gw, D).half().contiguous()
         hd = D // self.num_heads
         rpack = ops.pack_rel_tables(_rel_table(self.rel_pos_h, gh), _rel_table(self.rel_pos_w, gw), False, hd)
@@ -140,12 +144,15 @@ class Block(nn.Module):
 
     @torch.no_grad()
     def forward(self, x):
-        """image_encoder.py:174-193: x [B,64,64,dim] -> [B,64,64,dim] fp32: x + attn(norm1(x)) (14 x 14 windows with zero padding when
-        window_size > 0), then x + mlp(norm2(x)). The same launches as one block of `ImageEncoderViT._encode_patches` with the LayerNorms
+        """image_encoder.py:174-193: x [B,g,g,dim] -> [B,g,g,dim] fp32, g <= 64 (a global block: the side its rel-pos tables were built
+        for): x + attn(norm1(x)) (14 x 14 windows with zero padding when window_size > 0), then x + mlp(norm2(x)). The same launches as one block of `ImageEncoderViT._encode_patches` with the LayerNorms
         as passes of their own."""
         B, gh, gw, D = x.shape
-        if gh != gw or gh != 64 or not isinstance(self.mlp.act, nn.GELU):
-            raise NotImplementedError("Block.forward: SAM's 64 x 64 token map and GELU MLP (build_sam.py:66-81)")
+        K = self.window_size or gh
+        if (gh != gw or gh > 64 or not isinstance(self.mlp.act, nn.GELU) or not self.attn.use_rel_pos
+                or self.attn.rel_pos_h.shape[0] != 2 * K - 1 or self.attn.rel_pos_w.shape[0] != 2 * K - 1):
+            raise NotImplementedError("Block.forward: a square g x g token map, g <= 64, that matches the block's rel-pos tables "
+                                      "(2g - 1 rows for a global block), and a GELU MLP (build_sam.py:66-81)")
         bp = self._packed(gh)
         M = B * gh * gw
         hd = D // self.attn.num_heads
@@ -189,8 +196,9 @@ class ImageEncoderViT(nn.Module):
         self.grid = img_size // patch_size
         if not (use_abs_pos and use_rel_pos and qkv_bias):
             raise NotImplementedError("only SAM's configuration (abs pos + rel pos + qkv bias, build_sam.py:66-81)")
-        if self.grid != 64 or (embed_dim // num_heads) not in (64, 80):
-            raise NotImplementedError("HIP attention is built for the 64x64 token map and head dims 64 / 80")
+        if img_size % patch_size or not 1 <= self.grid <= 64 or (embed_dim // num_heads) not in (64, 80):
+            raise NotImplementedError("HIP attention is built for token maps up to 64 x 64 (img_size a multiple of patch_size) and "
+                                      "head dims 64 / 80")
         self.patch_embed = PatchEmbed((patch_size, patch_size), (patch_size, patch_size), in_chans=in_chans,
                                       embed_dim=embed_dim)
         self.pos_embed = nn.Parameter(torch.zeros(1, self.grid, self.grid, embed_dim))

@@ -91,8 +91,9 @@ class MaskDecoder(nn.Module):
             while len(self._ws) >= 4:          # (the transformer keeps the large per-shape buffers; these are ~1 MB per prompt set)
                 self._ws.pop(next(iter(self._ws)))
             e = lambda shape, dt=torch.float32: torch.empty(shape, dtype=dt, device=dev)  # noqa: E731
+            g4 = 4 * int(round(Nk ** 0.5))     # side of the low-res masks: two ConvTranspose(2, 2) over the g x g embedding
             self._ws[key] = dict(u1=e((B * Nk, 256)), h1=e((B, 4, 256)), h2=e((B, 4, 256)), hyper=e((B, 4, 32)), i1=e((B, 256)),
-                                 i2=e((B, 256)), iou=e((B, 4)), masks=e((B, 4, 256, 256)))
+                                 i2=e((B, 256)), iou=e((B, 4)), masks=e((B, 4, g4, g4)))
         return self._ws[key]
 
     # ---- the decoder ---------------------------------------------------------------------------------------------
@@ -102,11 +103,13 @@ class MaskDecoder(nn.Module):
         tokens fp32 [B,T,256] (output tokens ++ sparse prompts), dense_vec fp32 [256] (no-mask embedding),
         img_of_prompt int32 [B] (which image each prompt set belongs to; None = image 0).
         masks_out / iou_out: optional contiguous destinations (else views of the workspace, overwritten by the next call).
-        -> masks [B,4,256,256], iou [B,4]."""
+        -> masks [B,4,4g,4g] (g x g = Nk image tokens; 256 x 256 for SAM's 64 x 64 embedding), iou [B,4]."""
         pk = self._packed()
         B, T, _ = tokens.shape
         Nk = feat_tok.shape[-2]
-        g = int(Nk ** 0.5)
+        g = int(round(Nk ** 0.5))
+        if g * g != Nk:
+            raise NotImplementedError("a square g x g image embedding")
         if T > 16:
             raise NotImplementedError("more than 11 sparse prompt tokens per prompt set")
         ws = self._workspace(B, T, Nk, tokens.device)
