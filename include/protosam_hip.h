@@ -154,20 +154,25 @@ int psam_alp_sim(const float* qry, long long q_bstride, int ld, int B, int npix,
 int psam_alp_sim_pairs(const float* qry, long long q_bstride, int ld, int npix, int C, const void* tab, int n_entries,
                        int max_groups, float eps, float sim_scale, float* part, float* pred, void* stream);
 
-/* ---- resampling / packing -------------------------------------------------------------------------------------- */
+/* ---- resampling / packing --------------------------------------------------------------------------------------
+ * Every entry point of this section returns 1 before any launch (outputs untouched) when a count or an extent is not positive
+ * (B, planes, C, D, n, n_per_img, plane, IH, IW, OH, OW, H, W, S, P, ih, iw, oh, ow), and on the conditions named with it. */
 /* F.interpolate(img,(S,S),'bilinear') + im2col of a PxP/stride-P conv -> half [B*(S/P)^2, Kpad].
- * models/grid_proto_fewshot.py:88-89 + DINOv2 PatchEmbed; also SAM PatchEmbed when H == S. */
+ * models/grid_proto_fewshot.py:88-89 + DINOv2 PatchEmbed; also SAM PatchEmbed when H == S. Columns C*P*P .. Kpad-1 are zero.
+ * Status 1: S % P != 0, Kpad < C*P*P. */
 int psam_patchify_bilinear(const float* img, int B, int C, int H, int W, int S, int P, int Kpad, void* out, void* stream);
 /* F.interpolate(x, (OH,OW), 'bilinear', align_corners=False), fp32 planes. grid_proto_fewshot.py:272-273; ProtoSAM.py:592-594 */
 int psam_bilinear_nchw(const float* in, int planes, int IH, int IW, int OH, int OW, float* out, void* stream);
 /* The same resize in the conventions of the vendored SAM copies' postprocess_masks: mode 0 as above, 1 = bilinear
- * align_corners=True (SamBatched, modeling/sam.py:313-320), 2 = nearest (vendored Sam, modeling/sam.py:154-160). */
+ * align_corners=True (SamBatched, modeling/sam.py:313-320), 2 = nearest (vendored Sam, modeling/sam.py:154-160).
+ * Status 1: mode outside 0..2. */
 int psam_resize2d(const float* in, int planes, int IH, int IW, int OH, int OW, int mode, float* out, void* stream);
 /* token-major feature-map resize fp32 [B][ih*iw,C] -> [B][oh*ow,C] (the 32x32 upsample of grid_proto_fewshot.py:96-98) */
 int psam_bilinear_tokens(const float* in, long long in_bstride, int ld, int B, int ih, int iw, int C, int oh, int ow,
                          float* out, void* stream);
-/* [bilinear to OHxOW] -> softmax(dim=1) -> argmax for 2-class logits; prob fp32 [B,2,OH,OW], pred u8, fg_sum int[B].
- * models/ProtoSAM.py:592-602 */
+/* [bilinear to OHxOW] -> softmax(dim=1) -> argmax for 2-class logits; prob fp32 [B,2,OH,OW], pred u8, fg_sum int[B]
+ * (accumulated, caller zeroes; or NULL). With OW % 4 == 0 the rows are stored 16 bytes (prob) and 4 bytes (pred) at a time:
+ * prob must then be 16-byte and pred 4-byte aligned. models/ProtoSAM.py:592-602 */
 int psam_prob_argmax(const float* logits, int B, int IH, int IW, int OH, int OW, float* prob, void* pred, int* fg_sum,
                      void* stream);
 int psam_broadcast_rows(const float* row, int D, float* out, int B, long long stride, long long off, void* stream);
@@ -184,25 +189,29 @@ int psam_prob2_argmax(const float* scores, int P, int IH, int IW, int OH, int OW
  * zeroes; or NULL). Bit-identical to the two-launch chain. models/ProtoSAM.py:592-602 */
 int psam_scores_prob_argmax(const float* scores, int P, int GH, int GW, int IH, int IW, int OH, int OW, float* prob, void* pred,
                             int* fg_sum, void* stream);
-/* per-image min/max (order-preserving uint32 pairs).  models/ProtoSAM.py:660 */
+/* per-image min/max (order-preserving uint32 pairs); x needs 4-byte alignment only.  models/ProtoSAM.py:660 */
 int psam_minmax(const float* x, int B, long long n_per_img, void* mm, void* stream);
 /* ((x-min)/(max-min)*255).astype(uint8) -> (u8 - mean)/std -> im2col(16x16) half; mean3/std3 are HOST pointers.
- * models/ProtoSAM.py:651-660; modeling/sam.py:163-173; predictor.py:56-58,88. quantise 0 = ProtoMedSAM.py:203-205. */
+ * models/ProtoSAM.py:651-660; modeling/sam.py:163-173; predictor.py:56-58,88. quantise 0 = ProtoMedSAM.py:203-205.
+ * A constant image (max == min) divides by zero as the reference does: the call returns 0, the other images of the batch are
+ * unaffected, what that image's rows and u8out hold is unspecified. Status 1: S % P != 0, mean3 or std3 NULL. */
 int psam_sam_patchify(const float* img, const void* mm, int B, int S, int P, const float* mean3, const float* std3,
                       int quantise, void* out, void* u8out, void* stream);
-/* (x - mean[c]) / std[c] on [B,3,plane]; in_u8: x is uint8. mean3/std3 HOST pointers. modeling/sam.py:163-168 */
+/* (x - mean[c]) / std[c] on [B,3,plane]; in_u8: x is uint8. mean3/std3 HOST pointers (NULL: status 1). modeling/sam.py:163-168 */
 int psam_normalize_chw(const void* x, int in_u8, int B, long long plane, const float* mean3, const float* std3,
                        float* y, void* stream);
-/* im2col of the neck's 3x3/pad-1 conv on a token-major half map. image_encoder.py:98-104 */
+/* im2col of the neck's 3x3/pad-1 conv on a token-major half map (16-byte accesses). Status 1: C % 8 != 0. image_encoder.py:98-104 */
 int psam_im2col3x3(const void* in, int B, int H, int W, int C, void* out, void* stream);
+/* fp32 -> half, round to nearest even. Status 1: n % 8 != 0. x and y 16-byte aligned (as for the three passes below). */
 int psam_cast_f16(const float* x, void* y, long long n, void* stream);
 /* The element-wise passes of the reference-width mode of the SAM image encoder (every Linear of a block through psam_gemm_f32x3, fp32 in
  * and out): half -> fp32 (the attention output on its way to attn.proj, modeling/image_encoder.py:249; n % 8 == 0) and nn.GELU in its erf
- * form, in place on fp32 (MLPBlock, modeling/common.py:25-26; n % 4 == 0). */
+ * form, in place on fp32 (MLPBlock, modeling/common.py:25-26; n % 4 == 0). Status 1 otherwise. */
 int psam_cast_f32(const void* x, float* y, long long n, void* stream);
 int psam_gelu_f32(float* x, long long n, void* stream);
 /* fp32 -> fp16 pair hi = half(x), lo = half(x - hi) (write_hi = 0: hi is read, e.g. the copy a folded-LayerNorm GEMM wrote). Operands of
- * the split-fp16 GEMMs (hi W_hi + lo W_hi + hi W_lo) of the image encoder's neck: modeling/image_encoder.py:90-106. n % 8 == 0. */
+ * the split-fp16 GEMMs (hi W_hi + lo W_hi + hi W_lo) of the image encoder's neck: modeling/image_encoder.py:90-106. n % 8 == 0
+ * (status 1 otherwise, and for a NULL pointer). */
 int psam_split_f16(const float* x, void* hi, void* lo, long long n, int write_hi, void* stream);
 
 /* ---- connected components + per-component statistics ------------------------------------------------------------

@@ -46,7 +46,7 @@ __global__ void patchify_bilinear_kernel(const float* __restrict__ img, int B, i
 
 extern "C" int psam_patchify_bilinear(const float* img, int B, int C, int H, int W, int S, int P, int Kpad, void* out,
                                       void* stream) {
-  if (B <= 0 || S % P || Kpad < C * P * P) return PSAM_ERR_ARG;
+  if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || S <= 0 || P <= 0 || S % P || Kpad < C * P * P) return PSAM_ERR_ARG;
   const int np = (S / P) * (S / P);
   hipLaunchKernelGGL(patchify_bilinear_kernel, dim3(np, B), dim3(256), 0, (hipStream_t)stream, img, B, C, H, W, S, P,
                      Kpad, (half_t*)out);
@@ -174,7 +174,7 @@ __global__ __launch_bounds__(256) void prob_argmax_kernel(const float* __restric
 
 extern "C" int psam_prob_argmax(const float* logits, int B, int IH, int IW, int OH, int OW, float* prob, void* pred,
                                 int* fg_sum, void* stream) {
-  if (B <= 0) return PSAM_ERR_ARG;
+  if (B <= 0 || IH <= 0 || IW <= 0 || OH <= 0 || OW <= 0) return PSAM_ERR_ARG;
   hipLaunchKernelGGL(prob_argmax_kernel, dim3((OW + 1023) / 1024, OH, B), dim3(256), 0, (hipStream_t)stream, logits, IH,
                      IW, OH, OW, prob, (uint8_t*)pred, fg_sum);
   return psam_launch_status();
@@ -283,9 +283,11 @@ extern "C" int psam_minmax(const float* x, int B, long long n_per_img, void* mm,
 
 // quantise = 1: ProtoSAM (uint8 image, SAM pixel_mean/std). quantise = 0: ProtoMedSAM ([0,1] float image,
 // mean 0 / std 1, models/ProtoMedSAM.py:203-205).
+// A constant image (max == min) divides by zero, as the reference does: the call still returns 0 and the other images of the
+// batch are unaffected, but what that image's rows (and its u8out) hold is unspecified.
 extern "C" int psam_sam_patchify(const float* img, const void* mm, int B, int S, int P, const float* mean3,
                                  const float* std3, int quantise, void* out, void* u8out, void* stream) {
-  if (B <= 0 || S % P) return PSAM_ERR_ARG;
+  if (B <= 0 || S <= 0 || P <= 0 || S % P || !mean3 || !std3) return PSAM_ERR_ARG;
   const int np = (S / P) * (S / P);
   hipLaunchKernelGGL(sam_patchify_kernel, dim3(np, B), dim3(256), 0, (hipStream_t)stream, img, (const uint32_t*)mm, S,
                      P, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2], quantise, (half_t*)out,
@@ -311,7 +313,7 @@ __global__ void im2col3x3_kernel(const half_t* __restrict__ in, int H, int W, in
   }
 }
 extern "C" int psam_im2col3x3(const void* in, int B, int H, int W, int C, void* out, void* stream) {
-  if (B <= 0 || (C % 8) != 0) return PSAM_ERR_ARG;
+  if (B <= 0 || H <= 0 || W <= 0 || C <= 0 || (C % 8) != 0) return PSAM_ERR_ARG;
   hipLaunchKernelGGL(im2col3x3_kernel, dim3(H * W, B), dim3(256), 0, (hipStream_t)stream, (const half_t*)in, H, W, C,
                      (half_t*)out);
   return psam_launch_status();
@@ -409,7 +411,7 @@ __global__ void normalize_chw_kernel(const void* __restrict__ x, int in_u8, size
 }
 extern "C" int psam_normalize_chw(const void* x, int in_u8, int B, long long plane, const float* mean3,
                                   const float* std3, float* y, void* stream) {
-  if (B <= 0 || plane <= 0) return PSAM_ERR_ARG;
+  if (B <= 0 || plane <= 0 || !mean3 || !std3) return PSAM_ERR_ARG;
   const size_t total = (size_t)B * 3 * (size_t)plane;
   hipLaunchKernelGGL(normalize_chw_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x,
                      in_u8, (size_t)plane, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2], y, total);

@@ -101,6 +101,13 @@ def _req(t, dtype, name):
         raise ValueError(f"{name}: innermost dimension must be contiguous")
 
 
+def _req_aligned(t, nbytes, name):
+    """The kernel behind reads or writes `t` in `nbytes` pieces from its base pointer: a view that starts inside a storage, off
+    that boundary, is refused here, on the host, before any call into the library."""
+    if t is not None and t.data_ptr() % nbytes:
+        raise ValueError(f"{name}: data pointer must be {nbytes}-byte aligned (got a view at offset {t.data_ptr() % nbytes})")
+
+
 def gemm(a, w, bias=None, out=None, epilogue=EPI_F16, resid=None, gamma=None, resid_mod=0, out_seg=0,
          out_seg_stride=0, out_seg_off=0, M=None, out16=None, stats=None, ln_mr=None, ln_s=None):
     """out[M,N] = epi(a[M,K] @ w[N,K]^T + bias). a/w fp16 (K contiguous); out fp16 or fp32 by epilogue.
@@ -668,6 +675,8 @@ def prob_argmax(logits, OH, OW, prob=None, pred=None, fg_sum=None):
         prob = torch.empty((B, 2, OH, OW), dtype=torch.float32, device=logits.device)
     if pred is None:
         pred = torch.empty((B, OH, OW), dtype=torch.uint8, device=logits.device)
+    if OW % 4 == 0:                # the vector store path: 16 bytes of each probability row, 4 bytes of labels per lane
+        _req_aligned(prob, 16, "prob"); _req_aligned(pred, 4, "pred")
     h = _tstart("prob_argmax")
     st = _lib.lib().psam_prob_argmax(_ptr(logits), B, logits.shape[2], logits.shape[3], OH, OW, _ptr(prob), _ptr(pred),
                                     _ptr(fg_sum), _stream())
@@ -771,6 +780,7 @@ def cast_f16(x, out=None):
     assert x.is_contiguous()
     if out is None:
         out = torch.empty(x.shape, dtype=torch.float16, device=x.device)
+    _req_aligned(x, 16, "x"); _req_aligned(out, 16, "out")
     st = _lib.lib().psam_cast_f16(_ptr(x), _ptr(out), x.numel(), _stream())
     _lib.check(st, "psam_cast_f16")
     return out
@@ -783,6 +793,7 @@ def cast_f32(x, out=None):
     if out is None:
         out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
     _req(out, torch.float32, "out")
+    _req_aligned(x, 16, "x"); _req_aligned(out, 16, "out")
     st = _lib.lib().psam_cast_f32(_ptr(x), _ptr(out), x.numel(), _stream())
     _lib.check(st, "psam_cast_f32")
     return out
@@ -792,6 +803,7 @@ def gelu_f32_(x):
     """nn.GELU (erf form) in place on fp32 (the reference-width encoder mode, between lin1 and lin2)."""
     _req(x, torch.float32, "x")
     assert x.is_contiguous()
+    _req_aligned(x, 16, "x")
     st = _lib.lib().psam_gelu_f32(_ptr(x), x.numel(), _stream())
     _lib.check(st, "psam_gelu_f32")
     return x
@@ -807,6 +819,7 @@ def split_f16(x, hi=None, lo=None, write_hi=True):
     if lo is None:
         lo = torch.empty(x.shape, dtype=torch.float16, device=x.device)
     _req(hi, torch.float16, "hi"); _req(lo, torch.float16, "lo")
+    _req_aligned(x, 16, "x"); _req_aligned(hi, 16, "hi"); _req_aligned(lo, 16, "lo")
     st = _lib.lib().psam_split_f16(_ptr(x), _ptr(hi), _ptr(lo), x.numel(), 1 if write_hi else 0, _stream())
     _lib.check(st, "psam_split_f16")
     return hi, lo

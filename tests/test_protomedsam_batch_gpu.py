@@ -35,40 +35,47 @@ def _unpack(bits, S):
 
 
 # ---- kernels ----------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("IH", [73, 1024])
+# IH: the square input size of a 1024^2 output, or (IH, IW, OH, OW). The tuples are the edges test_resample_kernels_gpu.py anchors
+# psam_prob_argmax at: an odd output width (the per-pixel store path, a partly filled last group of four), non-square maps, and
+# the same-size path with an odd and with a multiple-of-four width.
+@pytest.mark.parametrize("IH", [73, 1024,
+                                pytest.param((41, 53, 251, 333), id="41x53-251x333"),
+                                pytest.param((73, 61, 3, 1023), id="73x61-3x1023"),
+                                pytest.param((47, 51, 47, 51), id="47x51-same"),
+                                pytest.param((64, 52, 64, 52), id="64x52-same")])
 def test_prob2_argmax_equals_chain(dev, IH):
     from protosam_amd import ops
-    S = 1024
+    IH, IW, OH, OW = IH if isinstance(IH, tuple) else (IH, IH, 1024, 1024)
     g = torch.Generator().manual_seed(7 + IH)
-    sc = torch.randn((12, 2, IH, IH), generator=g) * 4.0
-    ties = torch.randn((2, 1, IH, IH), generator=g)
-    sc = torch.cat([sc, ties.expand(2, 2, IH, IH),                          # exact ties everywhere: argmax -> class 0
-                    torch.stack([torch.full((IH, IH), 3.0), torch.full((IH, IH), -3.0)])[None]])   # no foreground at all
+    sc = torch.randn((12, 2, IH, IW), generator=g) * 4.0
+    ties = torch.randn((2, 1, IH, IW), generator=g)
+    sc = torch.cat([sc, ties.expand(2, 2, IH, IW),                          # exact ties everywhere: argmax -> class 0
+                    torch.stack([torch.full((IH, IW), 3.0), torch.full((IH, IW), -3.0)])[None]])   # no foreground at all
     sc[3, :, 5:40, 7:50] = 0.25                                               # a tied patch inside a random plane
     P = sc.shape[0]
     sc = sc.contiguous().to(dev)
     # the chain it replaces: resize, softmax + arg-max, softmax again (ProtoMedSAM.py:176-187, util/utils.py:485)
-    full = ops.bilinear_nchw(sc, S, S) if IH != S else sc
+    full = ops.bilinear_nchw(sc, OH, OW) if (IH, IW) != (OH, OW) else sc
     fg_ref = torch.zeros(P, dtype=torch.int32, device=dev)
-    prob_ref, pred_ref = ops.prob_argmax(full.contiguous(), S, S, fg_sum=fg_ref)
-    p2_ref, _ = ops.prob_argmax(prob_ref, S, S)
+    prob_ref, pred_ref = ops.prob_argmax(full.contiguous(), OH, OW, fg_sum=fg_ref)
+    p2_ref, _ = ops.prob_argmax(prob_ref, OH, OW)
     fg = torch.zeros(P, dtype=torch.int32, device=dev)
-    prob = torch.empty((P, 2, S, S), dtype=torch.float32, device=dev)
-    pred, pfg2 = ops.prob2_argmax(sc, S, S, fg_sum=fg, prob=prob)
+    prob = torch.empty((P, 2, OH, OW), dtype=torch.float32, device=dev)
+    pred, pfg2 = ops.prob2_argmax(sc, OH, OW, fg_sum=fg, prob=prob)
     assert torch.equal(pred, pred_ref)
     assert torch.equal(fg, fg_ref) and int(fg[-1]) == 0 and int(fg[-2]) == 0 and int(fg[0]) > 0
     d = (pfg2 - p2_ref[:, 1]).abs().max().item()
-    print(f"prob2_argmax {IH}->{S}: max |dpfg2| {d:.2e}")
+    print(f"prob2_argmax {IH}x{IW}->{OH}x{OW}: max |dpfg2| {d:.2e}")
     # pred and the counts are exact. The probabilities can differ from the chain in the last bit: bilinear_nchw_kernel resamples one
     # plane at a time, the fused kernels interpolate the two classes together (packed FMAs), so the compiler contracts the
     # interpolation's multiply-adds differently. prob_argmax with its own resize is the same arithmetic as the fused kernel.
     assert d <= 1e-6
     assert (prob - prob_ref).abs().max().item() <= 1e-6
-    prob_direct, pred_direct = ops.prob_argmax(sc, S, S)
+    prob_direct, pred_direct = ops.prob_argmax(sc, OH, OW)
     assert torch.equal(prob, prob_direct) and torch.equal(pred, pred_direct)
     # without the optional outputs
     fg2 = torch.zeros(P, dtype=torch.int32, device=dev)
-    pred2, pfg22 = ops.prob2_argmax(sc, S, S, fg_sum=fg2)
+    pred2, pfg22 = ops.prob2_argmax(sc, OH, OW, fg_sum=fg2)
     assert torch.equal(pred2, pred) and torch.equal(pfg22, pfg2) and torch.equal(fg2, fg)
 
 

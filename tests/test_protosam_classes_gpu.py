@@ -23,15 +23,24 @@ def _scores(P, g, seed, empty=()):
     return sc
 
 
+# O: the output size, square, or (OH, OW). The last cases are the edges test_resample_kernels_gpu.py anchors the chain at: an odd
+# output width (the per-pixel store path and a partly filled last group of four), a non-square output, and an output equal to the
+# image size (no second resize) with an odd and with a multiple-of-four width.
 @pytest.mark.parametrize("P,g,IH,IW,O", [(9, 37, 512, 512, 1024), (9, 73, 1024, 1024, 1024), (10, 37, 300, 517, 1024),
-                                          (9, 20, 97, 131, 250)])
+                                          (9, 20, 97, 131, 250),
+                                          pytest.param(9, 37, 300, 517, (1001, 999), id="9-37-300-517-1001x999"),
+                                          pytest.param(9, 20, 97, 131, (250, 333), id="9-20-97-131-250x333"),
+                                          pytest.param(9, 37, 301, 517, (301, 517), id="9-37-301-517-same"),
+                                          pytest.param(9, 20, 64, 48, (64, 48), id="9-20-64-48-same"),
+                                          pytest.param(9, 20, 97, 131, (3, 1025), id="9-20-97-131-3x1025")])
 def test_scores_prob_argmax_bit_identical(dev, P, g, IH, IW, O):
     from protosam_amd import ops
+    OH, OW = O if isinstance(O, tuple) else (O, O)
     sc = _scores(P, g, P + g, empty=(1, 4, 7)).to(dev)
     fg_ref = torch.zeros(P, dtype=torch.int32, device=dev)
-    prob_ref, pred_ref = ops.prob_argmax(ops.bilinear_nchw(sc, IH, IW), O, O, fg_sum=fg_ref)
+    prob_ref, pred_ref = ops.prob_argmax(ops.bilinear_nchw(sc, IH, IW), OH, OW, fg_sum=fg_ref)
     fg = torch.zeros(P, dtype=torch.int32, device=dev)
-    prob, pred = ops.scores_prob_argmax(sc, IH, IW, O, O, fg_sum=fg)
+    prob, pred = ops.scores_prob_argmax(sc, IH, IW, OH, OW, fg_sum=fg)
     torch.cuda.synchronize()
     assert torch.equal(prob, prob_ref) and torch.equal(pred, pred_ref) and torch.equal(fg, fg_ref)
     assert int(fg[1]) == 0 and int(fg.max()) > 0
