@@ -1102,13 +1102,17 @@ def mask_stats(low, first, nsel, MID, H, W, variant, thr=0.0, off=1.0, stats=Non
     return stats
 
 
-def plane_stats(planes, thr=0.0, off=1.0, binarize=True):
+def plane_stats(planes, thr=0.0, off=1.0, binarize=True, stats=None, out=None):
     """planes fp32 [n,H,W] -> (stats int32 [n,8] as mask_stats, uint8 [n,H,W] = plane > thr or None)."""
     _req(planes, torch.float32, "planes")
     assert planes.is_contiguous() and planes.dim() == 3
     n, H, W = planes.shape
-    stats = torch.empty((n, 8), dtype=torch.int32, device=planes.device)
-    out = torch.empty((n, H, W), dtype=torch.uint8, device=planes.device) if binarize else None
+    if stats is None:
+        stats = torch.empty((n, 8), dtype=torch.int32, device=planes.device)
+    if out is None and binarize:
+        out = torch.empty((n, H, W), dtype=torch.uint8, device=planes.device)
+    assert stats.dtype == torch.int32 and stats.is_contiguous() and stats.numel() >= n * 8
+    assert out is None or (out.dtype == torch.uint8 and out.is_contiguous() and out.numel() >= n * H * W)
     st = _lib.lib().psam_plane_stats(_ptr(planes), n, H, W, float(thr), float(off), _ptr(stats), _ptr(out), _stream())
     _lib.check(st, "psam_plane_stats")
     return stats, out
