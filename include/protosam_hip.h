@@ -22,7 +22,8 @@ extern "C" {
  * epilogue 0: half out;  1: half out = gelu_erf(.);  2: fp32 out = (resid ? resid[r,:] : 0) + (gamma ? gamma : 1)*(.)
  *   3: half out = relu(. + resid16[m,:]) with `resid` pointing at a HALF [*, ldr] map or null (conv + folded BatchNorm
  *   (+ identity) + ReLU of a torchvision ResNet Bottleneck; models/backbone/torchvision_backbones.py:19-23)
- *   resid row r = resid_mod ? m % resid_mod : m.  out row = out_seg ? (m/out_seg)*out_seg_stride + out_seg_off + m%out_seg : m.
+ *   resid row r = resid_mod ? m % resid_mod : m (epilogue 2 only: epilogue 3 reads its half residual at row m and rejects
+ *   resid_mod != 0 with status 1).  out row = out_seg ? (m/out_seg)*out_seg_stride + out_seg_off + m%out_seg : m.
  * N % 128 == 0, K % 64 == 0. Replaces every nn.Linear / 1x1 conv / patch-embed conv / ConvTranspose2d(2,2) GEMM:
  *   models/segment_anything/modeling/image_encoder.py:223-249 (qkv, proj), modeling/common.py:13-26 (MLPBlock),
  *   image_encoder.py:375-406 (PatchEmbed), :90-106 (neck), modeling/transformer.py:218-240 (image-side projections),
@@ -346,7 +347,8 @@ int psam_neg_points_batch(const int* labels, const float* pbg, long long pbg_str
  *   dataloaders/dataset_utils.py:76-108).
  * psam_volume_slices: out fp32 [Z,tile,S,S] = tile copies of cv2.resize((x - mean) * inv_std, (S,S), INTER_LINEAR) per slice
  *   (mode 0), or cv2.INTER_NEAREST of the raw values for label volumes (mode 1).
- *   dataloaders/ManualAnnoDatasetv2.py:165-187 (read_dataset), :317-327 (tile_z_dim). */
+ *   dataloaders/ManualAnnoDatasetv2.py:165-187 (read_dataset), :317-327 (tile_z_dim).
+ * Status 1 before any launch: n <= 0; Z, H, W, S or tile <= 0; mode outside 0 / 1; vol_dtype outside 0 .. 3. */
 int psam_volume_stats(const void* vol, int vol_dtype, long long n, float slope, float inter, double* out, void* stream);
 int psam_volume_slices(const void* vol, int vol_dtype, int Z, int H, int W, float slope, float inter, float mean,
                        float inv_std, int S, int tile, int mode, float* out, void* stream);
@@ -354,7 +356,12 @@ int psam_volume_slices(const void* vol, int vol_dtype, int Z, int H, int W, floa
 /* Convolution front-end of the ResNet-101 encoder (models/backbone/torchvision_backbones.py:12-52; torchvision's
  * deeplabv3_resnet101 backbone, output stride 8): im2col on token-major (NHWC) half maps for any kernel / stride / dilation /
  * padding, the 7x7 stride-2 stem straight from the fp32 NCHW image, and MaxPool2d(3, 2, 1). The convolutions themselves are
- * psam_gemm_f16 with BatchNorm folded into weights and bias (epilogue 3). */
+ * psam_gemm_f16 with BatchNorm folded into weights and bias (epilogue 3).
+ * psam_maxpool3x3s2 keeps the maximum with fmaxf, which drops a NaN where F.max_pool2d propagates it: its input is a post-ReLU
+ *   half map, which holds none.
+ * Status 1 before any launch: psam_im2col with B, H, W, C, kh, kw, stride or dil <= 0, pad < 0, C % 8, ldo % 8, ldo < kh*kw*C
+ *   or no output pixel (the map smaller than the dilated kernel); psam_im2col_stem with B, H or W <= 0, ldo < 147 (so 144) or
+ *   ldo % 8; psam_maxpool3x3s2 with B, H, W or C <= 0. */
 int psam_im2col(const void* in, int B, int H, int W, int C, int kh, int kw, int stride, int dil, int pad, int ldo, void* out,
                 void* stream);
 int psam_im2col_stem(const float* img, int B, int H, int W, int ldo, void* out, void* stream);
@@ -367,7 +374,9 @@ int psam_maxpool3x3s2(const void* in, int B, int H, int W, int C, void* out, voi
  * (affine grid + grid_sample NEAREST / aten _upsample_bilinear2d_aa), see oracle/rotate.py.
  * psam_rotate_nearest: planes [C,H,W] fp32 -> [C,outH,outW]; xg / yg = the base-grid linspace values of the (expanded)
  *   canvas, rt6 = host pointer to the 3x2 rescaled theta (row-major), crop_* = first canvas row / column kept.
- * psam_resize_aa: anti-aliased bilinear [C,H,W] -> [C,OH,OW] (tmp = fp32 scratch [C,H,OW]). */
+ *   The index arithmetic is written with round-to-nearest intrinsics, one per operation (no contraction): bit-reproducible.
+ * psam_resize_aa: anti-aliased bilinear [C,H,W] -> [C,OH,OW] (tmp = fp32 scratch [C,H,OW]).
+ * Status 1 before any launch: a non-positive extent, a negative crop, a null rt6 / xg / yg (rotate) or a null tmp (resize). */
 int psam_rotate_nearest(const float* src, float* dst, const float* xg, const float* yg, const float* rt6, int C, int H, int W,
                         int crop_y, int crop_x, int outH, int outW, void* stream);
 int psam_resize_aa(const float* src, float* tmp, float* dst, int C, int H, int W, int OH, int OW, void* stream);

@@ -1734,6 +1734,7 @@ static int gemm_dispatch(const void* A, const void* W, const float* bias, void* 
       (ldo % 4) != 0 || (resid && (ldr % 4) != 0))
     return PSAM_ERR_ARG;
   if (epilogue < 0 || epilogue > 3) return PSAM_ERR_ARG;
+  if (epilogue == EPI_RELU_F16 && resid_mod != 0) return PSAM_ERR_ARG;   // (its half residual is read at row m: no modulo form)
   GemmArgs p;
   p.A = (const half_t*)A;
   p.W = (const half_t*)W;

@@ -554,7 +554,9 @@ __global__ void im2col_kernel(const half_t* __restrict__ in, int H, int W, int C
 }
 extern "C" int psam_im2col(const void* in, int B, int H, int W, int C, int kh, int kw, int stride, int dil, int pad, int ldo,
                            void* out, void* stream) {
-  if (B <= 0 || (C % 8) != 0 || (ldo % 8) != 0 || ldo < kh * kw * C || stride <= 0 || dil <= 0) return PSAM_ERR_ARG;
+  if (B <= 0 || H <= 0 || W <= 0 || C <= 0 || kh <= 0 || kw <= 0 || pad < 0 || (C % 8) != 0 || (ldo % 8) != 0 || ldo < kh * kw * C ||
+      stride <= 0 || dil <= 0)
+    return PSAM_ERR_ARG;
   const int Ho = (H + 2 * pad - dil * (kh - 1) - 1) / stride + 1, Wo = (W + 2 * pad - dil * (kw - 1) - 1) / stride + 1;
   if (Ho <= 0 || Wo <= 0) return PSAM_ERR_ARG;
   hipLaunchKernelGGL(im2col_kernel, dim3(Ho * Wo, B), dim3(256), 0, (hipStream_t)stream, (const half_t*)in, H, W, C, kh, kw,
@@ -580,14 +582,15 @@ __global__ void im2col_stem_kernel(const float* __restrict__ img, int H, int W, 
   }
 }
 extern "C" int psam_im2col_stem(const float* img, int B, int H, int W, int ldo, void* out, void* stream) {
-  if (B <= 0 || ldo < 147 || (ldo % 8) != 0) return PSAM_ERR_ARG;
+  if (B <= 0 || H <= 0 || W <= 0 || ldo < 147 || (ldo % 8) != 0) return PSAM_ERR_ARG;
   const int Ho = (H + 6 - 7) / 2 + 1, Wo = (W + 6 - 7) / 2 + 1;
   hipLaunchKernelGGL(im2col_stem_kernel, dim3(Ho * Wo, B), dim3(64), 0, (hipStream_t)stream, img, H, W, Ho, Wo, ldo,
                      (half_t*)out);
   return psam_launch_status();
 }
 
-// MaxPool2d(3, stride 2, padding 1) on a token-major half map [B, H*W, C] -> [B, Ho*Wo, C]
+// MaxPool2d(3, stride 2, padding 1) on a token-major half map [B, H*W, C] -> [B, Ho*Wo, C]. fmaxf drops a NaN where
+// F.max_pool2d propagates it: the input is a post-ReLU half map, which holds none.
 __global__ void maxpool3x3s2_kernel(const half_t* __restrict__ in, int H, int W, int C, int Ho, int Wo,
                                     half_t* __restrict__ out) {
   const int pix = blockIdx.x, b = blockIdx.y;
@@ -603,7 +606,7 @@ __global__ void maxpool3x3s2_kernel(const half_t* __restrict__ in, int H, int W,
   }
 }
 extern "C" int psam_maxpool3x3s2(const void* in, int B, int H, int W, int C, void* out, void* stream) {
-  if (B <= 0 || C <= 0) return PSAM_ERR_ARG;
+  if (B <= 0 || H <= 0 || W <= 0 || C <= 0) return PSAM_ERR_ARG;
   const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
   hipLaunchKernelGGL(maxpool3x3s2_kernel, dim3(Ho * Wo, B), dim3(128), 0, (hipStream_t)stream, (const half_t*)in, H, W, C,
                      Ho, Wo, (half_t*)out);
@@ -639,7 +642,8 @@ __global__ void rotate_nearest_kernel(const float* __restrict__ src, float* __re
 }
 extern "C" int psam_rotate_nearest(const float* src, float* dst, const float* xg, const float* yg, const float* rt6, int C,
                                    int H, int W, int crop_y, int crop_x, int outH, int outW, void* stream) {
-  if (C <= 0 || H <= 0 || W <= 0 || outH <= 0 || outW <= 0 || crop_y < 0 || crop_x < 0 || !rt6) return PSAM_ERR_ARG;
+  if (C <= 0 || H <= 0 || W <= 0 || outH <= 0 || outW <= 0 || crop_y < 0 || crop_x < 0 || !rt6 || !xg || !yg)
+    return PSAM_ERR_ARG;
   hipLaunchKernelGGL(rotate_nearest_kernel, dim3((outW + 255) / 256, outH, C), dim3(256), 0, (hipStream_t)stream, src, dst,
                      xg, yg, rt6[0], rt6[1], rt6[2], rt6[3], rt6[4], rt6[5], H, W, crop_y, crop_x, outH, outW);
   return psam_launch_status();

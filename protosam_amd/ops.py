@@ -326,11 +326,14 @@ def im2col(x, B, H, W, C, kh, kw, stride, dil, pad, ldo=None, out=None):
     """token-major half map [B, H*W, C] -> half [B*Ho*Wo, ldo] (column (ky*kw+kx)*C + c; zero K padding up to ldo)."""
     _req(x, torch.float16, "x")
     assert x.is_contiguous()
-    Ho = (H + 2 * pad - dil * (kh - 1) - 1) // stride + 1
-    Wo = (W + 2 * pad - dil * (kw - 1) - 1) // stride + 1
+    Ho = (H + 2 * pad - dil * (kh - 1) - 1) // stride + 1 if stride > 0 else 0
+    Wo = (W + 2 * pad - dil * (kw - 1) - 1) // stride + 1 if stride > 0 else 0
     if ldo is None:
         ldo = kh * kw * C
     if out is None:
+        # sized from the same formulas as the library: what it would reject (status 1) must not reach the allocation
+        if min(B, H, W, C, kh, kw, stride, dil) <= 0 or pad < 0 or Ho <= 0 or Wo <= 0:
+            raise ValueError(f"im2col: no output for B={B} {H}x{W}x{C}, kernel {kh}x{kw} stride {stride} dil {dil} pad {pad}")
         out = torch.empty((B * Ho * Wo, ldo), dtype=torch.float16, device=x.device)
     st = _lib.lib().psam_im2col(_ptr(x), B, H, W, C, kh, kw, stride, dil, pad, ldo, _ptr(out), _stream())
     _lib.check(st, "psam_im2col")
@@ -355,31 +358,39 @@ def maxpool3x3s2(x, B, H, W, C, out=None):
     assert x.is_contiguous()
     Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
     if out is None:
+        if min(B, H, W, C) <= 0:      # (the library rejects these with status 1; no allocation from them)
+            raise ValueError(f"maxpool3x3s2: no output for B={B} {H}x{W}x{C}")
         out = torch.empty((B * Ho * Wo, C), dtype=torch.float16, device=x.device)
     st = _lib.lib().psam_maxpool3x3s2(_ptr(x), B, H, W, C, _ptr(out), _stream())
     _lib.check(st, "psam_maxpool3x3s2")
     return out, Ho, Wo
 
 
-def rotate_nearest(img, xg, yg, rt, crop_y, crop_x, out_h, out_w):
+def rotate_nearest(img, xg, yg, rt, crop_y, crop_x, out_h, out_w, out=None):
     """torchvision-style affine NEAREST resampling of fp32 [B,C,H,W] (protosam_amd/rotate.py); rt = host fp32 [3,2]."""
     _req(img, torch.float32, "img"); _req(xg, torch.float32, "xg"); _req(yg, torch.float32, "yg")
     assert img.is_contiguous() and rt.dtype == torch.float32 and rt.device.type == "cpu" and rt.is_contiguous()
     B, C, H, W = img.shape
-    out = torch.empty((B, C, out_h, out_w), dtype=torch.float32, device=img.device)
+    if out is None:
+        out = torch.empty((B, C, out_h, out_w), dtype=torch.float32, device=img.device)
+    _req(out, torch.float32, "out")
+    assert out.is_contiguous() and out.numel() >= B * C * max(out_h, 0) * max(out_w, 0)
     st = _lib.lib().psam_rotate_nearest(_ptr(img), _ptr(out), _ptr(xg), _ptr(yg), rt.data_ptr(), B * C, H, W, crop_y, crop_x,
                                         out_h, out_w, _stream())
     _lib.check(st, "psam_rotate_nearest")
     return out
 
 
-def resize_aa(img, oh, ow):
+def resize_aa(img, oh, ow, out=None):
     """anti-aliased bilinear resize of fp32 [B,C,H,W] (aten _upsample_bilinear2d_aa semantics)."""
     _req(img, torch.float32, "img")
     assert img.is_contiguous()
     B, C, H, W = img.shape
-    tmp = torch.empty((B * C, H, ow), dtype=torch.float32, device=img.device)
-    out = torch.empty((B, C, oh, ow), dtype=torch.float32, device=img.device)
+    tmp = torch.empty((B * C, H, max(ow, 0)), dtype=torch.float32, device=img.device)
+    if out is None:
+        out = torch.empty((B, C, oh, ow), dtype=torch.float32, device=img.device)
+    _req(out, torch.float32, "out")
+    assert out.is_contiguous() and out.numel() >= B * C * max(oh, 0) * max(ow, 0)
     st = _lib.lib().psam_resize_aa(_ptr(img), _ptr(tmp), _ptr(out), B * C, H, W, oh, ow, _stream())
     _lib.check(st, "psam_resize_aa")
     return out
