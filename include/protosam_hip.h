@@ -310,6 +310,26 @@ int psam_mask_binarize(const float* low, const int* idx, int n, int IN, int MID,
  * automatic_mask_generator.py:221-316; utils/amg.py:156-176, 303-346 */
 int psam_plane_stats(const float* planes, int n, int H, int W, float thr, float off, int* stats, void* out, void* stream);
 
+/* Uncompressed COCO run-length code of binary masks uint8 [n,H,W] (any non-zero byte is set), on the device: pixels in
+ * column-major order p = x*H + y, counts alternate zero-run / one-run lengths and start with a zero-run (a set first pixel
+ * gives a leading 0), at most H*W + 1 counts per mask. Replaces mask_to_rle_pytorch / rle_to_mask, utils/amg.py:107-149
+ * (called at automatic_mask_generator.py:312-313), without transposing the mask. No atomics: the output is bit-identical
+ * from run to run. Encoding is two calls, because the caller sizes `counts` from the totals in between:
+ * psam_rle_workspace: *ints_per_mask = int32 words of `cells` per mask; host arithmetic only, no launch.
+ * psam_rle_count: totals int64 [n] = number of counts of each mask; fills `cells` (int32 [n * ints_per_mask]) for
+ *   psam_rle_write. utils/amg.py:107-135
+ * psam_rle_write: offsets int64 [n+1] = exclusive running sum of totals (offsets[0] = 0); counts int32 [offsets[n]], mask i
+ *   at counts[offsets[i] .. offsets[i+1]). `masks` and `cells` unchanged since psam_rle_count. utils/amg.py:107-135
+ * psam_rle_decode: masks_out uint8 {0,1} [n,H,W] from `ends` int64 [offsets[n]] = the INCLUSIVE running sum of the flat
+ *   counts (over all masks) and the same offsets; a pixel past the end of a short list is 0. utils/amg.py:138-149
+ * Status 1 before any launch: n, H or W <= 0, H*W > 2^31 - 1, a null pointer. Any n (chunked inside over the grid limit). */
+int psam_rle_workspace(int H, int W, long long* ints_per_mask);
+int psam_rle_count(const unsigned char* masks, int n, int H, int W, int* cells, long long* totals, void* stream);
+int psam_rle_write(const unsigned char* masks, int n, int H, int W, const int* cells, const long long* offsets, int* counts,
+                   void* stream);
+int psam_rle_decode(const long long* ends, const long long* offsets, int n, int H, int W, unsigned char* masks_out,
+                    void* stream);
+
 /* Scoring: confusion counts and boxes of n (prediction plane, label plane) pairs in one launch, exact (integer atomics).
  * rows int32 [n,4] = (pred plane, pred value, label plane, label value); pixel i of a row is predicted iff
  * pred[pred plane][i] == pred value and true iff label[label plane][i] == label value (float planes compare by value).

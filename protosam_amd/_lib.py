@@ -86,6 +86,10 @@ SIGNATURES = {
     "psam_neg_points_batch": [c_void_p, c_void_p, c_longlong, c_void_p] + [c_int] * 6 + [c_float, c_void_p, c_void_p],
     "psam_mask_downscale": [c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p],
     "psam_plane_stats": [c_void_p, c_int, c_int, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p],
+    "psam_rle_workspace": [c_int, c_int, ctypes.POINTER(c_longlong)],
+    "psam_rle_count": [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p],
+    "psam_rle_write": [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
+    "psam_rle_decode": [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p],
     "psam_seg_counts": [c_void_p, c_int, c_int, c_longlong, c_void_p, c_int, c_int, c_longlong, c_int, c_int, c_void_p, c_int,
                         c_void_p, c_void_p],
     "psam_mask_binarize": [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p,

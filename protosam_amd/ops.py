@@ -1147,6 +1147,62 @@ def mask_binarize(low, idx, MID, H, W, variant, thr=0.0, label=None, out=None):
     return out, counts
 
 
+def _rle_masks(masks):
+    if not masks.is_cuda:
+        raise RuntimeError("masks: expected a device tensor (protosam_amd has no CPU path)")
+    if masks.dtype == torch.bool:
+        masks = masks.view(torch.uint8)
+    if masks.dtype != torch.uint8:
+        raise TypeError(f"masks: expected torch.uint8 or torch.bool, got {masks.dtype}")
+    if masks.dim() == 2:
+        masks = masks[None]
+    if masks.dim() != 3:
+        raise ValueError(f"masks: expected [n, H, W] or [H, W], got {tuple(masks.shape)}")
+    return masks.contiguous()
+
+
+def rle_encode(masks):
+    """masks uint8 / bool [n,H,W] or [H,W] (any non-zero byte is set) -> (counts int32 [total], offsets int64 [n+1]), both on the
+    device: mask i's uncompressed COCO run lengths (column-major, starting with a zero-run) are counts[offsets[i]:offsets[i+1]].
+    One scalar crosses to the host between the two launches (offsets[n], to size `counts`); it is the only synchronisation."""
+    masks = _rle_masks(masks)
+    n, H, W = masks.shape
+    dev = masks.device
+    offsets = torch.zeros((n + 1,), dtype=torch.int64, device=dev)
+    if n == 0:
+        return torch.empty((0,), dtype=torch.int32, device=dev), offsets
+    if H == 0 or W == 0:
+        raise ValueError(f"masks: empty planes {tuple(masks.shape)}")
+    L = _lib.lib()
+    per = _lib.c_longlong(0)
+    _lib.check(L.psam_rle_workspace(H, W, per), "psam_rle_workspace")
+    cells = torch.empty((n * per.value,), dtype=torch.int32, device=dev)
+    totals = torch.empty((n,), dtype=torch.int64, device=dev)
+    _lib.check(L.psam_rle_count(_ptr(masks), n, H, W, _ptr(cells), _ptr(totals), _stream()), "psam_rle_count")
+    torch.cumsum(totals, 0, out=offsets[1:])
+    counts = torch.empty((int(offsets[n].item()),), dtype=torch.int32, device=dev)
+    _lib.check(L.psam_rle_write(_ptr(masks), n, H, W, _ptr(cells), _ptr(offsets), _ptr(counts), _stream()), "psam_rle_write")
+    return counts, offsets
+
+
+def rle_decode(counts, offsets, H, W):
+    """The inverse of `rle_encode`: counts int32 [total], offsets int64 [n+1] (device) -> uint8 {0,1} [n,H,W]. The lists are taken
+    as they are (a pixel past the end of a short list is 0); `utils.amg.rle_to_mask_device` validates host-made lists."""
+    _req(counts, torch.int32, "counts"); _req(offsets, torch.int64, "offsets")
+    assert counts.dim() == 1 and offsets.dim() == 1 and offsets.numel() >= 1
+    n = offsets.numel() - 1
+    out = torch.empty((n, H, W), dtype=torch.uint8, device=counts.device)
+    if n == 0:
+        return out
+    off = offsets.cpu()                                        # n + 1 numbers: the kernel indexes `counts` with them
+    if int(off[0]) != 0 or bool((off[1:] < off[:-1]).any()) or int(off[-1]) > counts.numel() or counts.numel() == 0:
+        raise ValueError("offsets: expected 0 = offsets[0] <= ... <= offsets[n] <= len(counts), and at least one count")
+    ends = torch.cumsum(counts, 0, dtype=torch.int64)
+    st = _lib.lib().psam_rle_decode(_ptr(ends), _ptr(offsets), n, H, W, _ptr(out), _stream())
+    _lib.check(st, "psam_rle_decode")
+    return out
+
+
 _SEG_DT = {torch.int16: 0, torch.float32: 1, torch.uint8: 2, torch.int32: 3}      # (slice_io._TORCH_DT: the codes of psam_volume_*)
 SEG_COLS = ("tp", "fp", "fn", "tn", "px0", "py0", "px1", "py1", "gx0", "gy0", "gx1", "gy1")
 

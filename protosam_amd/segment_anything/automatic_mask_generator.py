@@ -9,7 +9,9 @@ happens:
   * box NMS (:262-268) runs on the host over the few hundred survivors of the score filters;
   * only the survivors of NMS are binarised (`psam_mask_binarize`), and they stay on the device until a caller asks
     for numpy (`generate`) - `SamWrapper` scores them against the label on the device and downloads one mask.
-The intermediate uncompressed RLE (:312-313) only exists when `output_mode` asks for it.
+The intermediate uncompressed RLE (:312-313) only exists when `output_mode` asks for it, and then it is made on the device
+(`mask_to_rle_pytorch` over `psam_rle_count` / `psam_rle_write`): the surviving masks are encoded in one call and only their
+run lengths cross to the host - no full-size mask is downloaded.
 
 `custom_points` keeps the reference's default, the *string* "false" (:52), and the reference's truthiness test (:280):
 with the default, the second half of every `points_per_batch` batch is labelled as NEGATIVE points. `custom_points=False`
@@ -21,15 +23,18 @@ take the SECOND resize of `postprocess_masks`, so the ones that pass the predict
 resolution in chunks and reduced by `psam_plane_stats` (counts, box, binary mask in one pass); edge filter, per-crop and
 cross-crop NMS on the host over the statistics; holes / islands below the area threshold are found with the device
 connected-components kernel (`psam_ccl`; the reference loops over masks with cv2, utils/amg.py:267-291).
-Not on this path (raise): output_mode "coco_rle" (pycocotools, same ImportError as the reference).
+output_mode "coco_rle" keeps the reference's contract: the constructor imports pycocotools and raises the same ImportError
+without it (:116-117); with it, the segmentation is `coco_encode_rle` of the uncompressed RLE (:181-183), which is this
+project's own restatement of the COCO string form. Without the package, `coco_encode_rle(rec["segmentation"])` on the
+records of output_mode "uncompressed_rle" gives the same COCO record.
 """
 import numpy as np
 import torch
 
 from .. import ops
 from .predictor import SamPredictor
-from .utils.amg import (box_xyxy_to_xywh, build_all_layer_point_grids, generate_crop_boxes,
-                        is_box_near_crop_edge, mask_to_rle, nms_xyxy)
+from .utils.amg import (area_from_rle, box_xyxy_to_xywh, build_all_layer_point_grids, coco_encode_rle, generate_crop_boxes,
+                        is_box_near_crop_edge, mask_to_rle_pytorch, nms_xyxy)
 
 
 class SamAutomaticMaskGenerator:
@@ -318,17 +323,30 @@ class SamAutomaticMaskGenerator:
         return data, masks
 
     # ---- public API --------------------------------------------------------------------------------------------------
+    def _segmentations(self, masks):
+        """uint8 device masks [n, H, W] of the final records -> their `segmentation` values (:176-183): bool arrays (the one
+        download of the masks), or RLEs encoded on the device in one call, of which only the run lengths are downloaded."""
+        if self.output_mode == "binary_mask":
+            return masks.cpu().numpy().astype(bool)
+        rles = mask_to_rle_pytorch(masks)
+        if self.output_mode == "coco_rle":
+            rles = [coco_encode_rle(r) for r in rles]
+        return rles
+
     @torch.no_grad()
     def generate(self, image):
         """image: HWC uint8 -> list of records {segmentation, area, bbox (XYWH), predicted_iou, point_coords,
-        stability_score, crop_box} (:139-192)."""
+        stability_score, crop_box} (:139-192). `segmentation` is a bool [H, W] array (output_mode "binary_mask"), the
+        uncompressed RLE {"size", "counts": [ints]} ("uncompressed_rle") or its COCO string form ("coco_rle", needs
+        pycocotools at construction as in the reference; `utils.amg.coco_encode_rle(rec["segmentation"])` on the
+        "uncompressed_rle" records gives the same COCO record without the package)."""
         if not self._fast_path(image):
             data, masks = self._generate_general(image)
-            masks = masks.cpu().numpy().astype(bool)
+            masks = self._segmentations(masks)
             anns = []
             for i in range(len(masks)):
                 anns.append({
-                    "segmentation": masks[i] if self.output_mode == "binary_mask" else mask_to_rle(masks[i]),
+                    "segmentation": masks[i],
                     "area": int(data["area"][i]),
                     "bbox": box_xyxy_to_xywh(data["boxes"][i]).tolist(),
                     "predicted_iou": float(data["iou_preds"][i]),
@@ -339,16 +357,12 @@ class SamAutomaticMaskGenerator:
             return anns
         cand = self._candidates(image)
         masks, _ = self._binarize(cand)
-        masks = masks.cpu().numpy().astype(bool)
+        masks = self._segmentations(masks)
         h, w = cand["size"]
         anns = []
         for i in range(len(masks)):
-            if self.output_mode == "binary_mask":
-                seg = masks[i]
-            else:
-                seg = mask_to_rle(masks[i])
             anns.append({
-                "segmentation": seg,
+                "segmentation": masks[i],
                 "area": int(cand["area"][i]),
                 "bbox": box_xyxy_to_xywh(cand["boxes"][i]).tolist(),
                 "predicted_iou": float(cand["iou_preds"][i]),

@@ -2,7 +2,9 @@
 
 Only the pieces that remain on the host once the per-candidate reductions run on the GPU (`psam_mask_stats`): the point
 grids (:179-199), crop boxes of layer 0 (:202-237), XYXY->XYWH (:92-96), the uncompressed column-major RLE
-(:108-153) and box NMS. `torchvision.ops.batched_nms` (a dependency absent from /root/reference; all categories are 0 in
+(:108-153) and box NMS. The RLE also exists on the device (`mask_to_rle_pytorch`, `rle_to_mask_device` over `psam_rle_*`; the
+host `mask_to_rle` / `rle_to_mask` stay as the reference the tests compare them with), and `coco_encode_rle` /
+`coco_decode_rle` (:294-300) restate the COCO API's published string form, so no pycocotools is needed for it. `torchvision.ops.batched_nms` (a dependency absent from /root/reference; all categories are 0 in
 the generator, so it is plain NMS) is restated from its published contract: visit boxes by decreasing score (stable),
 drop every later box whose IoU with a kept box exceeds the threshold, areas = (x2-x1)*(y2-y1) in fp32.
 """
@@ -57,6 +59,95 @@ def rle_to_mask(rle):
 
 def area_from_rle(rle):
     return sum(rle["counts"][1::2])
+
+
+def mask_to_rle_pytorch(tensor):
+    """utils/amg.py:107-135 on the HIP codec: device bool / uint8 [b, h, w] -> list of {"size": [h, w], "counts": [ints]}, equal
+    to `mask_to_rle` of every mask. The masks stay on the device (`ops.rle_encode`); one download of the run lengths and
+    their offsets serves the whole batch."""
+    import torch
+    from ... import ops
+    if tensor.dim() != 3:
+        raise ValueError(f"expected [b, h, w], got {tuple(tensor.shape)}")
+    b, h, w = tensor.shape
+    counts, offsets = ops.rle_encode(tensor)
+    packed = torch.cat([offsets, counts.to(torch.int64)]).cpu().numpy()
+    off, cnt = packed[:b + 1], packed[b + 1:]
+    return [{"size": [h, w], "counts": cnt[off[i]:off[i + 1]].tolist()} for i in range(b)]
+
+
+def rle_to_mask_device(rles, device):
+    """utils/amg.py:138-149 for a list of uncompressed RLEs of one size -> uint8 {0, 1} [n, h, w] on `device`
+    (`ops.rle_decode`). Every list is checked on the host first: a negative count, or counts that do not sum to h * w,
+    raise ValueError before anything is uploaded."""
+    import torch
+    from ... import ops
+    if len(rles) == 0:
+        raise ValueError("rle_to_mask_device needs at least one RLE (the size comes from it)")
+    h, w = (int(v) for v in rles[0]["size"])
+    if h <= 0 or w <= 0:
+        raise ValueError(f"bad size {rles[0]['size']}")
+    lists = []
+    for i, r in enumerate(rles):
+        if [int(v) for v in r["size"]] != [h, w]:
+            raise ValueError(f"rle {i}: size {r['size']} differs from {[h, w]}")
+        c = np.asarray(r["counts"], dtype=np.int64).reshape(-1)
+        if c.size and int(c.min()) < 0:
+            raise ValueError(f"rle {i}: negative count")
+        if int(c.sum()) != h * w:
+            raise ValueError(f"rle {i}: counts sum to {int(c.sum())}, not {h} * {w}")
+        lists.append(c)
+    offsets = np.concatenate([[0], np.cumsum([len(c) for c in lists])]).astype(np.int64)
+    counts = np.concatenate(lists).astype(np.int32)
+    return ops.rle_decode(torch.from_numpy(counts).to(device), torch.from_numpy(offsets).to(device), h, w)
+
+
+def coco_encode_rle(uncompressed_rle):
+    """utils/amg.py:294-300 without pycocotools: {"size", "counts": [ints]} -> {"size", "counts": str}, the COCO API's
+    compressed string (`rleToString`): each count from the third on is stored as its difference from the count two places
+    back, then written 5 bits at a time, low bits first, as chr(48 + bits) with 0x20 marking "more follows" (the sign is
+    carried by bit 0x10 of the last group)."""
+    cnts = [int(v) for v in uncompressed_rle["counts"]]
+    out = []
+    for i, x in enumerate(cnts):
+        if i > 2:
+            x -= cnts[i - 2]
+        more = True
+        while more:
+            c = x & 0x1f
+            x >>= 5
+            more = (x != -1) if (c & 0x10) else (x != 0)
+            if more:
+                c |= 0x20
+            out.append(chr(c + 48))
+    h, w = uncompressed_rle["size"]
+    return {"size": [h, w], "counts": "".join(out)}
+
+
+def coco_decode_rle(rle):
+    """The inverse of `coco_encode_rle` (the COCO API's `rleFrString`): {"size", "counts": str or bytes} -> uncompressed."""
+    s = rle["counts"]
+    if isinstance(s, str):
+        s = s.encode("ascii")
+    cnts = []
+    p = 0
+    while p < len(s):
+        x, k, more = 0, 0, True
+        while more:
+            if p >= len(s):
+                raise ValueError("truncated COCO RLE string")
+            c = s[p] - 48
+            x |= (c & 0x1f) << (5 * k)
+            more = bool(c & 0x20)
+            p += 1
+            k += 1
+            if not more and (c & 0x10):
+                x |= -1 << (5 * k)
+        if len(cnts) > 2:
+            x += cnts[-2]
+        cnts.append(x)
+    h, w = rle["size"]
+    return {"size": [h, w], "counts": cnts}
 
 
 def nms_xyxy(boxes, scores, iou_threshold):

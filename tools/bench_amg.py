@@ -1,6 +1,9 @@
 """Times SamWrapper.forward / SamAutomaticMaskGenerator.generate (32x32 grid, SAM ViT-H unless told otherwise).
 
-  python tools/bench_amg.py [--sam vit_h] [--depth N] [--iters 5] [--chunk 256] [--points 32]
+  python tools/bench_amg.py [--sam vit_h] [--depth N] [--iters 5] [--chunk 256] [--points 32] [--output-mode binary_mask]
+
+`--output-mode` is the generator's output_mode for the `generate` phase (binary_mask | uncompressed_rle | coco_rle); the other
+two phases do not depend on it.
 """
 import argparse
 import json
@@ -21,6 +24,7 @@ def main():
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--chunk", type=int, default=256)
     ap.add_argument("--points", type=int, default=32)
+    ap.add_argument("--output-mode", default="binary_mask", choices=["binary_mask", "uncompressed_rle", "coco_rle"])
     a = ap.parse_args()
     from protosam_amd.sam_wrapper import SamWrapper
     from protosam_amd.synth import synth_pair
@@ -35,14 +39,15 @@ def main():
     for name, gargs in (("defaults", {}),
                         ("keep_top64", dict(pred_iou_thresh=0.0, stability_score_thresh=0.0, box_nms_thresh=1.0))):
         w = SamWrapper({"model_type": a.sam, "sam_checkpoint": ck,
-                        "generator_args": dict(points_per_side=a.points, decode_chunk=a.chunk, **gargs)}).cuda()
+                        "generator_args": dict(points_per_side=a.points, decode_chunk=a.chunk, output_mode=a.output_mode,
+                                               **gargs)}).cuda()
         g = w.mask_generator
         if name == "keep_top64":
             cand = g._candidates(img)
             thr = float(np.sort(cand["iou_preds"])[-64])
             g.pred_iou_thresh = thr if thr > 0 else 1e-9
-        for phase in ("candidates", "wrapper"):
-            fn = (lambda: g._candidates(img)) if phase == "candidates" else (lambda: w(img, label))
+        for phase in ("candidates", "wrapper", "generate"):
+            fn = {"candidates": lambda: g._candidates(img), "wrapper": lambda: w(img, label), "generate": lambda: g.generate(img)}[phase]
             try:
                 fn()
             except TypeError:      # no proposal survived (defaults with synthetic weights)
@@ -57,7 +62,7 @@ def main():
         res[f"{name}_n_masks"] = w.last_stats.get("n_masks")
         del w
         torch.cuda.empty_cache()
-    res.update(sam=a.sam, depth=a.depth, points=a.points ** 2, chunk=a.chunk)
+    res.update(sam=a.sam, depth=a.depth, points=a.points ** 2, chunk=a.chunk, output_mode=a.output_mode)
     print(json.dumps(res))
 
 
