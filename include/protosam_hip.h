@@ -72,8 +72,12 @@ int psam_gemm_f16_splitk_ln(const void* A, const void* W, const float* bias, flo
 
 /* Tile override for psam_gemm_f16: 0 auto (default; also env PSAM_GEMM_TILE), 1 = 128x128x64 (HIP), 11 = 256x256x64 persistent
  * 8-wave kernel (HIP), 15 = assembly kernels (csrc/gemm_asm_gen.py, the default large tile), 16 = half-tile ping-pong assembly
- * kernels (csrc/gemm_asm2_gen.py, experimental); a tile that cannot take the call's layout falls back (16 -> 15 -> 11 -> 1). */
+ * kernels (csrc/gemm_asm2_gen.py, experimental), 17 = tile 15 with its k-loop on v_mfma_f32_16x16x32_f16 (same shapes as 15; within
+ * rounding of it, not bit-identical); a tile that cannot take the call's layout falls back (16 -> 15 -> 11 -> 1, 17 -> 11 -> 1). */
 int psam_gemm_set_tile(int tile);
+/* *tile = the tile the most recent psam_gemm_f16 / psam_gemm_f16_ln call of this process was dispatched to, after every fallback
+ * (0 before the first call): what tests and A/B tools check a forced tile against. */
+int psam_gemm_last_tile(int* tile);
 /* Schedule variant of the assembly GEMM (tile 15): 0 = the shipped kernels; n > 0 selects the numbered experiment kernels of a
  * library built with `make GENFLAGS=--experiments` (csrc/gemm_asm_gen.py; a missing variant makes the next GEMM return an error). */
 int psam_gemm_asm_variant(int variant);
@@ -81,7 +85,9 @@ int psam_gemm_asm_variant(int variant);
  * assembly kernels for the large tiles, "half_tiles" (PSAM_GEMM_HALF) the half-tile assembly kernels for shapes with few 256x256
  * tiles, "splitk" (PSAM_GEMM_SPLITK), "nsplit" (PSAM_GEMM_NSPLIT) the column split of one-slice fc1 shapes; "max_wgs"
  * (PSAM_GEMM_MAX_WGS, an integer, 0 = none) caps the persistent grids of the assembly kernels - two streams then run their GEMMs
- * side by side on disjoint CUs. Unknown name: error. */
+ * side by side on disjoint CUs; "mfma16" (PSAM_GEMM_MFMA16) what the automatic choice does where it would pick tile 15: 0 keep 15,
+ * 1 take tile 17 wherever it is eligible, negative / unset the measured per-shape rule (csrc/gemm.hip mfma16_auto). Unknown name:
+ * error. */
 int psam_gemm_set_option(const char* name, int value);
 /* Device scratch for the split-K form of psam_gemm_f16 (fp32 partial sums, [ksplit][M][N]): used only when registered and
  * large enough; EPI 2 on few 256x256 tiles with K >= 2048 then runs `ksplit` workgroups per tile + one reduce pass

@@ -25,6 +25,7 @@ SIGNATURES = {
     "psam_gemm_f16_splitk_ln": [c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 7 + [c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_int,
                                 c_void_p],
     "psam_gemm_set_tile": [c_int],
+    "psam_gemm_last_tile": [ctypes.POINTER(c_int)],
     "psam_gemm_asm_variant": [c_int],
     "psam_gemm_set_option": [ctypes.c_char_p, c_int],
     "psam_gemm_set_workspace": [c_void_p, c_size_t],

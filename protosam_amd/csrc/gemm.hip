@@ -1341,9 +1341,12 @@ static const hipFunction_t* asm_load(int family = 1) {
   if (it != m->fns.end()) return it->second.data();
   // [0..2]: f16 / gelu / f32; [3..5] (family 1, shipped schedule): the same with the default cache policy in the epilogue (_l2);
   // [6..8]: the folded-LayerNorm forms (_ln: consumers f16 / gelu, producer f32)
+  // family 3 (tile 17): the family-1 kernels on v_mfma_f32_16x16x32_f16 (_m16; streaming epilogue only: [3..5] = [0..2])
   const char* names[3] = {"f16", "gelu", "f32"};
-  const char* suffix[3] = {"", "_l2", "_ln"};
-  const int nf = (family == 1 && g_asm_variant == 0) ? 9 : 3;
+  const char* suffix1[3] = {"", "_l2", "_ln"};
+  const char* suffix3[3] = {"_m16", "_m16", "_ln_m16"};
+  const char* const* suffix = family == 3 ? suffix3 : suffix1;
+  const int nf = (family != 2 && g_asm_variant == 0) ? 9 : 3;
   std::vector<hipFunction_t> f(9, nullptr);
   for (int i = 0; i < nf; ++i) {
     std::string n = std::string(family == 2 ? "psam_gemm_asm2_" : "psam_gemm_asm_") + names[i % 3] + suffix[i / 3] +
@@ -1407,10 +1410,12 @@ static const AsmTable* asm_table(int ntm, int ntn, int mode, int halves = 0, int
   }
   return &(g_asm_tabs[key] = t);
 }
-// lnf: 0 plain, 1 a folded-LayerNorm launch (tile 15 has _ln forms of its kernels, tile 16 none)
-static bool asm_eligible(const GemmArgs& p, int epilogue, int lnf) {
+// lnf: 0 plain, 1 a folded-LayerNorm launch (tiles 15 and 17 have _ln forms of their kernels, tile 16 none)
+// family 3 (tile 17) takes exactly what family 1 (tile 15) takes
+static bool asm_eligible(const GemmArgs& p, int epilogue, int lnf, int family = 1) {
+  if (family == 3 && !asm_load(3)) return false;
   if (lnf) {
-    const hipFunction_t* f = asm_load(1);
+    const hipFunction_t* f = asm_load(family);
     const bool cons = p.ln_mr || p.ln_s, prod = p.out16 || p.stats;
     if (!f || g_asm_variant != 0 || (cons && prod)) return false;
     if (cons && (!f[6 + epilogue] || !p.ln_mr || !p.ln_s || !p.bias || (reinterpret_cast<uintptr_t>(p.ln_mr) & 15) || (reinterpret_cast<uintptr_t>(p.ln_s) & 15))) return false;
@@ -1450,16 +1455,16 @@ static int launch_asm(const GemmArgs& p, int epilogue, hipStream_t s, int family
   if (!fns) return PSAM_ERR_LAUNCH;
   // family 2 walks 256x128 half-tiles in the same XCD-aware order: the workgroups of an XCD that run side by side then share A panels
   // (one workgroup doing both halves of a 256x256 tile back to back re-read its A panel from beyond the L2: measured 20 % slower on fc2)
-  const int ntm = (p.M + 255) / 256, ntn = family >= 2 ? p.N / 128 : p.N / 256;
+  const int ntm = (p.M + 255) / 256, ntn = family == 2 ? p.N / 128 : p.N / 256;
   const AsmTable* t = asm_table(ntm, ntn, pick_map_mode(ntm, ntn));
   if (!t) return PSAM_ERR_LAUNCH;
   AsmGemmArgs a;
   a.A = p.A; a.W = p.W; a.bias = p.bias; a.out = p.out; a.resid = p.resid; a.gamma = p.gamma; a.tab = t->dev;
   a.M = p.M; a.N = p.N; a.K = p.K; a.lda = p.lda; a.ldw = p.ldw; a.ldo = p.ldo; a.ldr = p.resid ? p.ldr : 0; a.G = t->grid;
   a.flags = p.gamma ? 1 : 0;
-  a.pad = (family == 1 && p.resid_mod > 0) ? p.resid_mod - 1 : -1;      // (S_RMASK of gemm_asm_gen.py; the half-tile kernels ignore it)
+  a.pad = (family != 2 && p.resid_mod > 0) ? p.resid_mod - 1 : -1;      // (S_RMASK of gemm_asm_gen.py; the half-tile kernels ignore it)
   a.trace = nullptr;
-  const bool ln_cons = family == 1 && p.ln_mr && p.ln_s, ln_prod = family == 1 && (p.out16 || p.stats);
+  const bool ln_cons = family != 2 && p.ln_mr && p.ln_s, ln_prod = family != 2 && (p.out16 || p.stats);
   if (ln_cons) {   // folded LayerNorm, consumer: (mean, rstd) rows + -mean fragments in `resid`, the s fragments (behind the N floats) in `gamma`
     a.resid = p.ln_mr;
     a.gamma = p.ln_s + p.N;
@@ -1488,7 +1493,7 @@ static int launch_asm(const GemmArgs& p, int epilogue, hipStream_t s, int family
     for (int b = 0; b < t->grid; ++b) rt += h[(size_t)t->grid * 4 + b * 4];
     for (int b = 0; b < t->grid; ++b) { loop += h[b * 4]; epi += h[b * 4 + 1]; kt += h[b * 4 + 2]; tot += h[b * 4 + 3]; tmax = h[b * 4 + 3] > tmax ? h[b * 4 + 3] : tmax; }
     const double tiles = kt / (p.K / 64);
-    if (kt > 0) fprintf(stderr, "asm v%d %dx%dx%d epi%d: %.0f cycles per K-tile, %.0f cycles per epilogue (%.1f tiles per workgroup) kernel entry to exit: mean %.0f max %u cycles = %.1f us (shader clock %.0f MHz)\n", g_asm_variant, p.M, p.N,
+    if (kt > 0) fprintf(stderr, "asm%s v%d %dx%dx%d epi%d: %.0f cycles per K-tile, %.0f cycles per epilogue (%.1f tiles per workgroup) kernel entry to exit: mean %.0f max %u cycles = %.1f us (shader clock %.0f MHz)\n", family == 3 ? " m16" : "", g_asm_variant, p.M, p.N,
                         p.K, epilogue, loop / kt, epi / tiles, tiles / t->grid, tot / t->grid, tmax, rt / t->grid * 0.01, rt > 0 ? tot / rt * 100.0 : 0.0);
   }
   return PSAM_OK;
@@ -1654,28 +1659,55 @@ extern "C" int psam_gemm_f16_splitk_ln(const void* A, const void* W, const float
 
 // tile choice: 0 = auto; 1 = 128x128x64, four waves, two workgroups per CU (HIP); 11 = 256x256x64 persistent 8-wave kernel (HIP; the
 // folded-LayerNorm, head-major and split-K forms live here); 15 = the assembly kernels of gemm_asm_gen.py (256x256 tiles, four
-// waves, the default large tile); 16 = the half-tile ping-pong assembly kernels of gemm_asm2_gen.py (experimental). The other
+// waves, the default large tile); 16 = the half-tile ping-pong assembly kernels of gemm_asm2_gen.py (experimental); 17 = tile 15
+// with its k-loop on v_mfma_f32_16x16x32_f16 (same shapes, same fallbacks; not bit-identical to 15: another summation order). The other
 // HIP schedules of rounds 1 / 2 (tiles 2 ... 10, 13, 14) lost to these and are gone (history: DESIGN.md).
 // (PSAM_GEMM_TILE env var or psam_gemm_set_tile)
 // dispatch switches (A/B and tests): initial values from the environment, psam_gemm_set_option overrides at run time
-enum { OPT_ASM = 0, OPT_HALF, OPT_SPLITK, OPT_NSPLIT, OPT_DEEP, OPT_SMALL, OPT_COUNT };
-static const char* const g_opt_names[OPT_COUNT] = {"asm", "half_tiles", "splitk", "nsplit", "deep", "small"};
-static const char* const g_opt_env[OPT_COUNT] = {"PSAM_GEMM_ASM", "PSAM_GEMM_HALF", "PSAM_GEMM_SPLITK", "PSAM_GEMM_NSPLIT", "PSAM_GEMM_DEEP", "PSAM_GEMM_SMALL"};
-static int g_opt[OPT_COUNT] = {-1, -1, -1, -1, -1, -1};
+// "mfma16" has three states: 0 never replace tile 15 by tile 17, 1 replace it wherever tile 17 is eligible, unset (or set to a
+// negative value) the measured rule mfma16_auto() - gemm_option() reports the unset state as 2
+enum { OPT_ASM = 0, OPT_HALF, OPT_SPLITK, OPT_NSPLIT, OPT_DEEP, OPT_SMALL, OPT_MFMA16, OPT_COUNT };
+static const char* const g_opt_names[OPT_COUNT] = {"asm", "half_tiles", "splitk", "nsplit", "deep", "small", "mfma16"};
+static const char* const g_opt_env[OPT_COUNT] = {"PSAM_GEMM_ASM", "PSAM_GEMM_HALF", "PSAM_GEMM_SPLITK", "PSAM_GEMM_NSPLIT", "PSAM_GEMM_DEEP", "PSAM_GEMM_SMALL",
+                                                 "PSAM_GEMM_MFMA16"};
+static int g_opt[OPT_COUNT] = {-1, -1, -1, -1, -1, -1, -1};
 static int gemm_option(int i) {
-  if (g_opt[i] < 0) { const char* e = getenv(g_opt_env[i]); g_opt[i] = e ? (atoi(e) != 0) : 1; }
+  if (g_opt[i] < 0) { const char* e = getenv(g_opt_env[i]); g_opt[i] = (e && atoi(e) >= 0) ? (atoi(e) != 0) : (i == OPT_MFMA16 ? 2 : 1); }
   return g_opt[i];
 }
 extern "C" int psam_gemm_set_option(const char* name, int value) {
   if (name && strcmp(name, "max_wgs") == 0) { g_max_wgs = value > 0 ? value : 0; return PSAM_OK; }
   for (int i = 0; i < OPT_COUNT; ++i)
-    if (name && strcmp(name, g_opt_names[i]) == 0) { g_opt[i] = value != 0; return PSAM_OK; }
+    if (name && strcmp(name, g_opt_names[i]) == 0) { g_opt[i] = (i == OPT_MFMA16 && value < 0) ? 2 : value != 0; return PSAM_OK; }
   return PSAM_ERR_ARG;
+}
+static int g_last_tile = 0;
+extern "C" int psam_gemm_last_tile(int* tile) {
+  if (!tile) return PSAM_ERR_ARG;
+  *tile = g_last_tile;
+  return PSAM_OK;
 }
 static int g_tile_override = -1;
 extern "C" int psam_gemm_set_tile(int t) {
   g_tile_override = t;
   return PSAM_OK;
+}
+// Where tile 17 (the 16x16x32 form of tile 15) replaces tile 15 by default. Under the power cap the chip holds a higher clock on the
+// 16x16 shape (tools/micro/mfma_power_bench.hip, profiles/mfma_shape_power.txt: 1.15x the FLOP/s from registers, 1.13x with every
+// fragment re-read from LDS, at ~1 % more cycles per FLOP), and the k-loop costs the same cycles per K-tile (2180-2250 against
+// 2220-2250). Per shape, tools/gemm_mfma_ab.py (profiles/gemm_mfma16_by_shape.txt; wall TFLOP/s, median of 7 alternating rounds,
+// tile 15 -> tile 17; rounds = 256-tiles per CU), the eight encoder launches of a 32-slice step:
+//   fp16 + LN consumer    131072x3840x1280 (30 rounds)  1235 -> 1309   41504x2304x768 (5.7)  1061 -> 1131
+//   GELU + LN consumer    131072x5120x1280 (40)         1115 -> 1184   41504x3072x768 (7.6)   959 ->  993
+//   fp32 + LN producer    131072x1280x1280 (10)          797 ->  829   41504x768x768  (1.9)   514 ->  530
+//   fp32 + LN producer    131072x1280x5120 (10)         1143 -> 1206   41504x768x3072 (1.9)  1003 -> 1063
+// Every class gains 3-7 %, more than the spread of tile 15's rounds. The rule covers what was measured: all three epilogues, K >= 768,
+// at least 1.9 rounds of tiles, and an output beyond the size below which tile 15 runs its default-cache-policy (_l2) kernels -
+// tile 17 has the streaming epilogue only.
+static bool mfma16_auto(int M, int N, int K, int epilogue) {
+  const long t256 = (long)((M + 255) / 256) * (N / 256), ncu = eff_cus();
+  const size_t out_bytes = (size_t)M * N * (epilogue == EPI_F32 ? 4 : 2);
+  return K >= 768 && t256 * 10 >= ncu * 19 && out_bytes > ((size_t)48 << 20);
 }
 static int pick_tile(int M, int N, int K, int epilogue) {
   if (g_tile_override < 0) {
@@ -1703,7 +1735,9 @@ static int pick_tile(int M, int N, int K, int epilogue) {
     const int fill = short_f32 ? 95 : (epilogue == EPI_F32 || rounds > 1) ? 80 : 50;
     if (K >= 768 && t256 * 100 >= rounds * ncu * fill) {
       // the assembly kernels (tile 15) take every shape the persistent HIP kernel took, when eligible (gemm_dispatch)
-      return gemm_option(OPT_ASM) ? 15 : 11;
+      if (!gemm_option(OPT_ASM)) return 11;
+      const int m16 = gemm_option(OPT_MFMA16);
+      return (m16 == 1 || (m16 == 2 && mfma16_auto(M, N, K, epilogue))) ? 17 : 15;
     }
   }
   // too few 256x256 tiles for the CUs (one slice through proj / fc1 / fc2: 80 ... 320 tiles): the half-tile assembly kernels have
@@ -1772,7 +1806,8 @@ static int gemm_dispatch(const void* A, const void* W, const float* bias, void* 
   // the assembly kernels (tile 15) take plain row-major operands; everything else they were picked for goes to the persistent HIP kernel
   if (tsel == 16 && !asm2_eligible(p, epilogue, ln_prod || ln_cons)) tsel = (g_tile_override > 0 || ln_prod || ln_cons) ? 15 : 1;
   if (tsel == 15 && !asm_eligible(p, epilogue, ln_prod || ln_cons)) tsel = (N % 256 == 0) ? 11 : 1;
-  if (tsel != 1 && tsel != 11 && tsel != 12 && tsel != 13 && tsel != 15 && tsel != 16) tsel = (N % 256 == 0) ? 11 : 1;   // (tiles 2 ... 14 of rounds 1 / 2 are gone)
+  if (tsel == 17 && !asm_eligible(p, epilogue, ln_prod || ln_cons, 3)) tsel = (N % 256 == 0) ? 11 : 1;     // (falls back as 15 does)
+  if (tsel != 1 && tsel != 11 && tsel != 12 && tsel != 13 && tsel != 15 && tsel != 16 && tsel != 17) tsel = (N % 256 == 0) ? 11 : 1;   // (tiles 2 ... 14 of rounds 1 / 2 are gone)
   if (tsel == 11 && (N % 256) != 0) tsel = 1;
   if (tsel == 11 && epilogue != EPI_F32 && !p.wide16) tsel = 1;   // the persistent kernel stores fp16 rows with 16-byte instructions
   if (ln_cons && !p.wide16) return PSAM_ERR_ARG;                  // (the folded-LayerNorm epilogues live in tiles 1 and 11)
@@ -1786,8 +1821,10 @@ static int gemm_dispatch(const void* A, const void* W, const float* bias, void* 
       if (seen[key]++ == 0) fprintf(stderr, "psam_gemm_f16: %s\n", key);
     }
   }
+  g_last_tile = tsel;
   if (tsel == 15) return launch_asm(p, epilogue, s);
   if (tsel == 16) return launch_asm(p, epilogue, s, 2);
+  if (tsel == 17) return launch_asm(p, epilogue, s, 3);
   p.ksplit = 1;
   p.ks_ws = nullptr;
   // split-K (see launch8kp_splitk): only where the automatic choice fell back to the 128x128 kernel because too few 256-tiles

@@ -106,6 +106,9 @@ class Gen(AsmWriter):
         # fp32 epilogue (no bias, no residual) stores range r's partial sums to plane r of `out`
         self.sk = bool(sched.get("splitk")) and epi == EPI_F32 and not self.lnp
         assert not (self.sk and sched.get("trace"))
+        # sched "mfma": "32x32x16" (4x4 blocks of 16 accumulators, 64 MFMA slots per K-tile) or "16x16x32" (8x8 blocks of 4, 128 slots)
+        self.m16 = sched.get("mfma", "32x32x16") == "16x16x32"
+        assert not (self.m16 and (self.sk or sched.get("deep_ring") or sched.get("stagger")))
 
     # ------------------------------------------------------------ pieces of the program
     def item_rows_cols(self, item):
@@ -191,6 +194,93 @@ class Gen(AsmWriter):
             return "ds_read_b128 v[%d:%d], v%d offset:%d" % (V_SET[st] + 4 * idx, V_SET[st] + 4 * idx + 3, V_FA + ks, idx * 4096)
         j = idx - 4
         return "ds_read_b128 v[%d:%d], v%d offset:%d" % (V_SET[st] + 16 + 4 * j, V_SET[st] + 16 + 4 * j + 3, V_FB + ks, j * 4096)
+
+    # The 16x16x32 form. A fragment is 16 rows x 4 sixteen-byte k-slots: lane -> row lane & 15, slot 4 * k-step + (lane >> 4), for X
+    # and W alike (the MFMA's own k order: lane group g supplies k = 8 g ... 8 g + 7 of its 32), read at the same swizzled place
+    # row * 128 + ((slot ^ (row >> 1) & 7) << 4) the DMA wrote it to. Sixteen lanes of a group cover 16 distinct 16-byte columns of
+    # two 128-byte row parities: conflict-free like the 32-row form. A k-step's 8 X + 8 W fragments fill two of the four register
+    # sets (k-step 0: S0 S1 = v32..95, k-step 1: S2 S3 = v96..159): +0..31 X fragments of row blocks 0..7, +32..63 W of column blocks.
+    RD16_ORDER = tuple(range(8, 16)) + tuple(range(8))        # W fragments first: MFMA slot 0 needs all eight and X block 0
+    M16_FA, M16_FB = (1, 2), (3, 8)                           # read addresses of the X / W fragments per k-step
+
+    def frag_read16(self, ks, idx):
+        """idx 0..7: X fragment of 16-row block idx; 8..15: W fragment of 16-column block idx - 8 - of k-step ks (0 / 1)"""
+        base = V_SET[2 * ks]
+        if idx < 8:
+            return "ds_read_b128 v[%d:%d], v%d offset:%d" % (base + 4 * idx, base + 4 * idx + 3, self.M16_FA[ks], idx * 2048)
+        j = idx - 8
+        return "ds_read_b128 v[%d:%d], v%d offset:%d" % (base + 32 + 4 * j, base + 32 + 4 * j + 3, self.M16_FB[ks], j * 2048)
+
+    def mfma16(self, ks, rb, cb, zero):
+        """D^T block: lane owns output row rb * 16 + (lane & 15) and the columns cb * 16 + 4 (lane >> 4) + 0..3 in a[blk:blk+3]"""
+        blk, base = (rb * 8 + cb) * 4, V_SET[2 * ks]
+        a = "v[%d:%d]" % (base + 32 + 4 * cb, base + 32 + 4 * cb + 3)
+        b = "v[%d:%d]" % (base + 4 * rb, base + 4 * rb + 3)
+        cc = "0" if zero else "a[%d:%d]" % (blk, blk + 3)
+        return "v_mfma_f32_16x16x32_f16 a[%d:%d], %s, %s, %s" % (blk, blk + 3, a, b, cc)
+
+    def build_slots16(self, zero_copy=False):
+        """side instructions behind each of the 128 MFMAs of a K-tile (slot = k-step * 64 + rb * 8 + cb): at most one per 16-cycle gap
+        (a compare and its branch take two gaps), a DMA piece alone in its gap with its m0 in the gap before. zero_copy: the slots of
+        k-step 0 as the C = 0 copy of a tile's first K-tile carries them (own return label of the tile switch; no operand requests:
+        a tile has at least two K-tiles)"""
+        sc = self.sched
+        z = "_z" if zero_copy else ""
+        slots = [[] for _ in range(128)]
+        def put(s, ins):
+            assert not slots[s], (s, ins, slots[s])
+            slots[s].append(ins)
+        # fragment reads of k-step 1 of THIS tile during k-step 0
+        for i, idx in enumerate(self.RD16_ORDER):
+            if not sc.get("no_reads"):
+                put(sc["rd1"][i], self.frag_read16(1, idx))
+        for i, r in enumerate((self.M16_FA[1], self.M16_FB[1])):
+            put(sc["tog1"][i], "v_xor_b32 v%d, 0x%x, v%d" % (r, LDS_BUF, r))
+        if not sc.get("no_epilogue") and not zero_copy:
+            put(sc["pre_slot"], "s_cmp_eq_u32 s%d, 1" % S_KREM)
+            slots[sc["pre_slot"] + 1] += ["s_cbranch_scc1 L_pre_%s" % self.name, "L_pre_ret_%s:" % self.name]
+        # barrier A: every wave has its fragments of this K-tile -> its buffer may be refilled
+        a = sc["barA"]
+        if not sc.get("no_barrier"):
+            slots[a] += ["s_waitcnt lgkmcnt(0)", "s_barrier"]
+        put(a + 1, "s_cmp_eq_u32 s%d, 0" % S_DKREM)
+        slots[a + 2] += ["s_cbranch_scc1 L_switch%s_%s" % (z, self.name), "L_switch_ret%s_%s:" % (z, self.name)]
+        # DMA pieces of K-tile t+2
+        for p in range(16):
+            s = sc["dma"][p]
+            assert p == 0 or s - sc["dma"][p - 1] >= 3
+            if sc.get("no_dma"):
+                continue
+            put(s - 1, self.dma_m0(p))
+            put(s, self.dma_issue(p))
+        # barrier B: K-tile t+1 has landed
+        b = sc["barB"]
+        issued = sum(1 for p in range(16) if sc["dma"][p] <= b)
+        if not sc.get("no_barrier"):
+            assert not slots[b]
+            slots[b] += ["s_waitcnt vmcnt(%d)" % (0 if sc.get("no_dma") else issued), "s_barrier"]
+        # fragment reads of k-step 0 of the NEXT K-tile, then the DMA side's advance
+        for i, idx in enumerate(self.RD16_ORDER):
+            assert sc["rd0"][i] > b
+            if not sc.get("no_reads"):
+                put(sc["rd0"][i], self.frag_read16(0, idx))
+        for i, ins in enumerate(self.dma_advance()):
+            assert sc["adv"] + i > sc["dma"][15]
+            put(sc["adv"] + i, ins)
+        return slots
+
+    def lgkm_waits16(self):
+        """slot -> operand of the s_waitcnt in front of its MFMA. LDS reads complete in order: the sixteen of k-step 0 were issued
+        W0..7, X0..7 at the end of the previous K-tile, X block rb is needed at slot 8 rb; by then the reads of k-step 1 issued in
+        this K-tile's earlier gaps are outstanding too. From barrier A on (lgkmcnt(0)) everything has arrived."""
+        sc = self.sched
+        out = {}
+        for rb in range(8):
+            s = 8 * rb
+            if s > sc["barA"]:
+                break
+            out[s] = min(15, (7 - rb) + sum(1 for x in sc["rd1"] if x < s))
+        return out
 
     def mfma(self, st, rb, cb, zero):
         blk = (rb * 4 + cb) * 16
@@ -397,6 +487,11 @@ class Gen(AsmWriter):
                 vm += [("bg", 0), ("bg", 0)]
             self.resid_loads(0, vm)
             self.resid_loads(1, vm)
+        elif self.m16:             # a lane's columns: cb * 16 + 4 (lane >> 4) + 0..3 -> v180..211
+            for cb in range(8):
+                r = self.F16_BIAS + cb * 4
+                e("buffer_load_dwordx4 v[%d:%d], v%d, s[%d:%d], s%d offen offset:%d" % (r, r + 3, V_TMP + 11, SRD_BIAS, SRD_BIAS + 3, S_N0X4, cb * 64))
+                vm.append(("bias", 0))
         else:
             for cb in range(4):
                 for q in range(4):
@@ -416,6 +511,20 @@ class Gen(AsmWriter):
         e("s_lshl_b32 s%d, s%d, 12" % (S_T2, S_T1))                     # col0 * 16 bytes
         e("s_lshl_b32 s%d, s%d, 12" % (S_T3, S_T0))                     # row0 * 16
         e("s_lshl_b32 s%d, s%d, 11" % (S_T4, S_T0))                     # row0 * 8
+        if self.m16:
+            # 16x16 blocks: the rank-1 update is one v_mfma_f32_16x16x16_f16 per block, whose operands are the first 8 bytes of a
+            # fragment row (k = 0..3 of lanes 0..15; lanes 16..63 read beyond the buffer = 0): s of the eight column blocks in
+            # v212..227, -mean of the eight row blocks in v228..243, rstd in four register pairs (M16_RSTD)
+            for cb in range(8):
+                e("buffer_load_dwordx2 v[%d:%d], v%d, s[%d:%d], s%d offen offset:%d" % (self.M16_SF + 2 * cb, self.M16_SF + 2 * cb + 1, V_SFOFF, SRD_SF, SRD_SF + 3, S_T2, cb * 256))
+                vm.append(("sf", 0))
+            for rb in range(8):
+                e("buffer_load_dwordx2 v[%d:%d], v%d, s[%d:%d], s%d offen offset:%d" % (self.M16_MF + 2 * rb, self.M16_MF + 2 * rb + 1, V_MFOFF, SRD_MF, SRD_MF + 3, S_T3, rb * 256))
+                vm.append(("mf", 0))
+            for rb in range(8):
+                e("buffer_load_dword v%d, v%d, s[%d:%d], s%d offen offset:%d" % (self.M16_RSTD[rb >> 1] + (rb & 1), V_RSOFF, SRD_MR, SRD_MR + 3, S_T4, rb * 128))
+                vm.append(("rs", 0))
+            return vm
         for cb in range(4):
             e("buffer_load_dwordx4 v[%d:%d], v%d, s[%d:%d], s%d offen offset:%d" % (96 + 4 * cb, 99 + 4 * cb, V_SFOFF, SRD_SF, SRD_SF + 3, S_T2, cb * 512))
             vm.append(("sf", 0))
@@ -427,10 +536,66 @@ class Gen(AsmWriter):
             vm.append(("rs", 0))
         return vm
 
+    M16_SF, M16_MF = 212, 228
+    M16_RSTD = (28, 30, 4, 6)                    # aligned pairs; v4..v7 are free: the 16x16x32 form has two read addresses per operand (M16_FA / M16_FB)
+
     def younger(self, vm, tag):
         return younger(vm, tag)
 
+    def epilogue_f16_m16(self, gelu, vm):
+        """the fp16 epilogues of the 16x16x32 form: the PARK half differs (a 32-row slab is 2 x 8 blocks of 4 registers; a lane's four
+        columns cb * 16 + 4 g + 0..3 are half of the 16-byte chunk 2 cb + (g >> 1) of its row), the emit half is epilogue_f16's"""
+        e = self.e
+        self.c("---- epilogue (16x16x32 accumulators): bias (+ GELU) -> fp16, through the wave's slab so that 16 lanes store one 256-byte row piece")
+        e("s_nop 7")
+        e("s_nop 7")
+        self.tile_offsets(2)
+        e("v_add_u32 v%d, s%d, v%d" % (V_O, S_TOFF, V_OLANE))
+        e("s_waitcnt vmcnt(%d)" % self.younger(vm, ("bias", 0)))
+        if self.lnc:
+            self.c("folded LayerNorm: acc -= mean_row * s_col, one rank-1 MFMA per 16x16 block (fp16 hi / lo operands: fp32-accurate)")
+            e("s_waitcnt vmcnt(%d)" % self.younger(vm, ("rs", 0)))
+            for rb in range(8):
+                for cb in range(8):
+                    blk = (rb * 8 + cb) * 4
+                    e("v_mfma_f32_16x16x16_f16 a[%d:%d], v[%d:%d], v[%d:%d], a[%d:%d]" % (blk, blk + 3, self.M16_SF + 2 * cb, self.M16_SF + 2 * cb + 1,
+                                                                                      self.M16_MF + 2 * rb, self.M16_MF + 2 * rb + 1, blk, blk + 3))
+            e("s_nop 7")
+            e("s_nop 7")
+            e("s_nop 3")
+        for rb32 in range(4):
+            em = self.F16_EM[rb32 & 1]
+            for sub in range(2):
+                rb = 2 * rb32 + sub
+                for cb in range(8):
+                    blk = (rb * 8 + cb) * 4
+                    t = V_TMP
+                    for i in range(4):
+                        e("v_accvgpr_read_b32 v%d, a%d" % (t + i, blk + i))
+                    b = self.F16_BIAS + cb * 4
+                    if self.lnc:
+                        rp, hs = self.M16_RSTD[rb >> 1], rb & 1
+                        for hh in range(2):
+                            e("v_pk_fma_f32 v[%d:%d], v[%d:%d], v[%d:%d], v[%d:%d] op_sel:[0,%d,0] op_sel_hi:[1,%d,1]" % (
+                                t + 2 * hh, t + 2 * hh + 1, t + 2 * hh, t + 2 * hh + 1, rp, rp + 1, b + 2 * hh, b + 2 * hh + 1, hs, hs))
+                    else:
+                        e("v_pk_add_f32 v[%d:%d], v[%d:%d], v[%d:%d]" % (t, t + 1, t, t + 1, b, b + 1))
+                        e("v_pk_add_f32 v[%d:%d], v[%d:%d], v[%d:%d]" % (t + 2, t + 3, t + 2, t + 3, b + 2, b + 3))
+                    if gelu:
+                        self.gelu_quad(t, self.F16_EM[(rb32 + 1) & 1], t + 2, self.F16_EM[(rb32 + 1) & 1] + 8)
+                    e("v_cvt_pk_f16_f32 v%d, v%d, v%d" % (t, t, t + 1))
+                    e("v_cvt_pk_f16_f32 v%d, v%d, v%d" % (t + 1, t + 2, t + 3))
+                    e("ds_write_b64 v%d, v[%d:%d] offset:%d" % (V_PARK + cb, t, t + 1, sub * 4096))
+            for it in range(8):
+                e("ds_read_b128 v[%d:%d], v%d offset:%d" % (em + 4 * it, em + 4 * it + 3, V_EADDR + (it & 3), (it >> 2) * 4096))
+            for it in range(8):
+                e("s_waitcnt lgkmcnt(%d)" % (7 - it))
+                e("buffer_store_dwordx4 v[%d:%d], v%d, s[%d:%d], 0 offen%s" % (em + 4 * it, em + 4 * it + 3, V_O, SRD_O, SRD_O + 3, self.sched.get("store_policy", "")))
+                e("v_add_u32 v%d, s%d, v%d" % (V_O, S_ROW4, V_O))
+
     def epilogue_f16(self, gelu, vm):
+        if self.m16:
+            return self.epilogue_f16_m16(gelu, vm)
         e = self.e
         self.c("---- epilogue: bias (+ GELU) -> fp16, through the wave's slab so that 16 lanes store one 256-byte row piece")
         e("s_nop 7")
@@ -486,6 +651,8 @@ class Gen(AsmWriter):
         # 4 / 6: all eight slabs in flight by the time the third is parked. Measured: no change (23.7k vs 24.3k cycles per epilogue
         # at 65536x1280x1280, wall equal) - the epilogue is not bound by the number of requests a wave's registers can hold.
         e("s_nop 7")
+        if self.m16:
+            e("s_nop 7")
         self.tile_offsets(4)
         e("v_add_u32 v%d, s%d, v%d" % (V_O, S_TOFF, V_OLANE))
         if self.lnp:
@@ -512,7 +679,12 @@ class Gen(AsmWriter):
             after_slab = dict((j, j + 3) for j in range(5))
         for slab in range(8):
             rb, h = slab >> 1, slab & 1
-            for cbl in range(2):
+            if self.m16:         # 2 x 4 blocks of 4 registers: the lane's columns cbl * 16 + 4 g + 0..3 of the slab are its row's chunk 4 cbl + g
+                for sub in range(2):
+                    for cbl in range(4):
+                        blk = ((2 * rb + sub) * 8 + 4 * h + cbl) * 4
+                        e("ds_write_b128 v%d, a[%d:%d] offset:%d" % (V_PARK + cbl, blk, blk + 3, sub * 4096))
+            for cbl in range(0 if self.m16 else 2):
                 for q in range(4):
                     blk = (rb * 4 + 2 * h + cbl) * 16 + 4 * q
                     e("ds_write_b128 v%d, a[%d:%d]" % (V_PARK + cbl * 4 + q, blk, blk + 3))
@@ -634,8 +806,9 @@ class Gen(AsmWriter):
         e("v_lshrrev_b32 v%d, 6, v0" % V_T0)
         e("s_nop 1")
         e("v_readfirstlane_b32 s%d, v%d" % (S_WV, V_T0))
-        e("v_and_b32 v%d, 31, v%d" % (V_LR, V_LANE))
-        e("v_lshrrev_b32 v%d, 5, v%d" % (V_LG, V_LANE))
+        # lane -> (row of an MFMA block, k group): 32 rows x 2 groups, or 16 x 4 in the 16x16x32 form
+        e("v_and_b32 v%d, %d, v%d" % (V_LR, 15 if self.m16 else 31, V_LANE))
+        e("v_lshrrev_b32 v%d, %d, v%d" % (V_LG, 4 if self.m16 else 5, V_LANE))
         e("s_waitcnt lgkmcnt(0)")
         e("s_lshr_b32 s%d, s%d, 1" % (S_WR, S_WV))
         e("s_and_b32 s%d, s%d, 1" % (S_WC, S_WV))
@@ -692,12 +865,12 @@ class Gen(AsmWriter):
         e("v_lshrrev_b32 v%d, 1, v%d" % (V_T0, V_LR))
         e("v_and_b32 v%d, 7, v%d" % (V_T0, V_T0))                          # sw = (lr >> 1) & 7
         e("v_lshlrev_b32 v%d, 7, v%d" % (V_T1, V_LR))                      # lr * 128
-        for ks in range(4):
-            e("v_or_b32 v%d, %d, v%d" % (V_T2, 2 * ks, V_LG))
+        for ks in range(2 if self.m16 else 4):
+            e("v_or_b32 v%d, %d, v%d" % (V_T2, (4 if self.m16 else 2) * ks, V_LG))
             e("v_xor_b32 v%d, v%d, v%d" % (V_T2, V_T2, V_T0))
             e("v_lshl_add_u32 v%d, v%d, 4, v%d" % (V_T2, V_T2, V_T1))
-            e("v_add_u32 v%d, s%d, v%d" % (V_FA + ks, S_FA, V_T2))
-            e("v_add_u32 v%d, s%d, v%d" % (V_FB + ks, S_FB, V_T2))
+            e("v_add_u32 v%d, s%d, v%d" % (self.M16_FA[ks] if self.m16 else V_FA + ks, S_FA, V_T2))
+            e("v_add_u32 v%d, s%d, v%d" % (self.M16_FB[ks] if self.m16 else V_FB + ks, S_FB, V_T2))
         # ---- DMA offsets: piece j covers rows j*32 + wv*8 + lane/8, LDS slot lane%8 <- source chunk slot ^ ((row>>1)&7)
         e("v_lshrrev_b32 v%d, 3, v%d" % (V_T0, V_LANE))
         e("s_lshl_b32 s%d, s%d, 3" % (S_T0, S_WV))
@@ -719,7 +892,20 @@ class Gen(AsmWriter):
         e("v_and_b32 v%d, 15, v%d" % (V_T0, V_LR))                          # lr & 15
         e("v_lshlrev_b32 v%d, 8, v%d" % (V_T1, V_LR))                       # lr * 256
         e("v_add_u32 v%d, s%d, v%d" % (V_T1, S_T0, V_T1))
-        if self.epi == EPI_F32:
+        if self.m16 and self.epi == EPI_F32:
+            e("v_xor_b32 v%d, v%d, v%d" % (V_T0, V_T0, V_LG))                # row ^ g
+            for cbl in range(4):                                            # chunk16 = cbl*4 (+ g)
+                e("v_xor_b32 v%d, %d, v%d" % (V_T2, 4 * cbl, V_T0))
+                e("v_lshl_add_u32 v%d, v%d, 4, v%d" % (V_PARK + cbl, V_T2, V_T1))
+        elif self.m16:
+            e("v_lshrrev_b32 v%d, 1, v%d" % (V_T2, V_LG))
+            e("v_xor_b32 v%d, v%d, v%d" % (V_T0, V_T0, V_T2))                # row ^ (g >> 1)
+            e("v_and_b32 v%d, 1, v%d" % (V_T2, V_LG))
+            e("v_lshl_add_u32 v%d, v%d, 3, v%d" % (V_T1, V_T2, V_T1))        # + (g & 1) * 8
+            for cb in range(8):                                             # chunk16 = cb*2 (+ g >> 1)
+                e("v_xor_b32 v%d, %d, v%d" % (V_T2, 2 * cb, V_T0))
+                e("v_lshl_add_u32 v%d, v%d, 4, v%d" % (V_PARK + cb, V_T2, V_T1))
+        elif self.epi == EPI_F32:
             e("v_xor_b32 v%d, v%d, v%d" % (V_T0, V_T0, V_LG))                # (lr & 15) ^ lg
             for cq in range(8):                                             # chunk16 = cbl*8 + 2q (+ lg)
                 e("v_xor_b32 v%d, %d, v%d" % (V_T2, (cq >> 2) * 8 + 2 * (cq & 3), V_T0))
@@ -808,7 +994,7 @@ class Gen(AsmWriter):
             e("v_add_u32 v%d, s%d, v%d" % (V_T1, S_T0, V_T0))
             e("v_add_u32 v%d, s%d, v%d" % (V_T2, S_T1, V_T0))
             e("v_mov_b32 v%d, 0x40000000" % V_T3)                             # lanes 32..63 (k = 8..15): far beyond the buffers -> zeros
-            e("v_cmp_eq_u32 vcc, 1, v%d" % V_LG)
+            e(("v_cmp_ne_u32 vcc, 0, v%d" if self.m16 else "v_cmp_eq_u32 vcc, 1, v%d") % V_LG)     # (16x16x32 form: lanes 16..63)
             e("v_cndmask_b32 v%d, v%d, v%d, vcc" % (V_T1, V_T1, V_T3))
             e("v_cndmask_b32 v%d, v%d, v%d, vcc" % (V_T2, V_T2, V_T3))
             e("v_lshlrev_b32 v%d, 3, v%d" % (V_T0, V_LR))                     # (lane & 31) * 8: (mean, rstd) row
@@ -858,6 +1044,49 @@ class Gen(AsmWriter):
             e("s_mov_b32 s%d, s%d" % (S_KREM, S_NK))
         e("s_waitcnt vmcnt(16)")
         e("s_barrier")
+        if self.m16:
+            self.kloop16()
+        else:
+            self.kloop32()
+        self.after_kloop()
+
+    def kloop16(self):
+        """the K-tile loop of the 16x16x32 form: 2 k-steps of 64 MFMAs; k-step 0 exists twice (C = 0 for a tile's first K-tile)"""
+        e, n = self.e, self.name
+        for idx in self.RD16_ORDER:
+            e(self.frag_read16(0, idx))
+        for r in (self.M16_FA[0], self.M16_FB[0]):
+            e("v_xor_b32 v%d, 0x%x, v%d" % (r, LDS_BUF, r))
+        slots, zslots, waits = self.build_slots16(), self.build_slots16(True), self.lgkm_waits16()
+        def run(sl, lo, hi, zero):
+            for s in range(lo, hi):
+                if s in waits:
+                    e("s_waitcnt lgkmcnt(%d)" % waits[s])
+                e(self.mfma16(s // 64, (s % 64) // 8, s % 8, zero))
+                for ins in sl[s]:
+                    if ins.endswith(":"):
+                        self.lab(ins[:-1])
+                    else:
+                        e(ins)
+        self.lab("L_tile_begin_%s" % n)
+        if self.sched.get("trace"):
+            e("s_memtime s[%d:%d]" % (S_TS0, S_TS0 + 1))
+        run(zslots, 0, 64, True)
+        e("s_branch L_after_ks0_%s" % n)
+        self.L.append(".p2align 4")
+        self.lab("L_loop_%s" % n)
+        run(slots, 0, 64, False)
+        self.lab("L_after_ks0_%s" % n)
+        run(slots, 64, 128, False)
+        e("s_xor_b32 s%d, s%d, 0x%x" % (S_M0BASE, S_M0BASE, LDS_BUF))
+        for r in (self.M16_FA[0], self.M16_FB[0]):
+            e("v_xor_b32 v%d, 0x%x, v%d" % (r, LDS_BUF, r))
+        e("s_sub_u32 s%d, s%d, 1" % (S_KREM, S_KREM))
+        e("s_cmp_eq_u32 s%d, 0" % S_KREM)
+        e("s_cbranch_scc0 L_loop_%s" % n)
+
+    def kloop32(self):
+        e, n = self.e, self.name
         for i in range(16):
             e(self.frag_read(i // 8, i // 8, i % 8))
         for r in (V_FA, V_FA + 1, V_FB, V_FB + 1):
@@ -891,6 +1120,10 @@ class Gen(AsmWriter):
         e("s_sub_u32 s%d, s%d, 1" % (S_KREM, S_KREM))
         e("s_cmp_eq_u32 s%d, 0" % S_KREM)
         e("s_cbranch_scc0 L_loop_%s" % n)
+
+    def after_kloop(self):
+        e, n = self.e, self.name
+        esize = 4 if self.epi == EPI_F32 else 2
         # ---- tile finished
         if self.sched.get("trace"):
             e("s_memtime s[%d:%d]" % (S_TS1, S_TS1 + 1))
@@ -900,6 +1133,7 @@ class Gen(AsmWriter):
             e("s_add_u32 s%d, s%d, s%d" % (S_NKT, S_NKT, S_NK))
         # memory operations between the operand requests of the last K-tile and the epilogue: that K-tile's DMA pieces
         n_dma_after = 0 if self.sched.get("no_dma") else sum(1 for p in range(16) if self.sched["dma"][p] > self.sched.get("pre_slot", 17))
+        assert not self.m16 or n_dma_after in (0, 16)
         if self.sched.get("no_epilogue"):
             pass
         else:
@@ -908,7 +1142,8 @@ class Gen(AsmWriter):
             vm = self.pre_epilogue()
             self.pre_code = self.L
             self.L = pre_lines
-            n_late = 0 if self.sched.get("no_dma") else sum(1 for p in range(16) if self.sched["dma"][p] > 48)
+            # (the 16x16x32 form requests the folded-LayerNorm operands with the others: all sixteen pieces follow)
+            n_late = n_dma_after if self.m16 else 0 if self.sched.get("no_dma") else sum(1 for p in range(16) if self.sched["dma"][p] > 48)
             vm += [("dma", 0)] * (n_dma_after - n_late)
             if self.lnc:
                 pre_lines = self.L
@@ -963,11 +1198,17 @@ class Gen(AsmWriter):
         self.lab("L_switch_%s" % n)
         self.switch_tile()
         e("s_branch L_switch_ret_%s" % n)
+        if self.m16:               # the same from the C = 0 copy of k-step 0
+            self.lab("L_switch_z_%s" % n)
+            self.switch_tile()
+            e("s_branch L_switch_ret_z_%s" % n)
         if not self.sched.get("no_epilogue"):
             self.lab("L_pre_%s" % n)
             self.L += self.pre_code
+            if self.lnc and self.m16:
+                self.L += self.pre2_code
             e("s_branch L_pre_ret_%s" % n)
-            if self.lnc:
+            if self.lnc and not self.m16:
                 self.lab("L_pre2_%s" % n)
                 self.L += self.pre2_code
                 e("s_branch L_pre2_ret_%s" % n)
@@ -999,6 +1240,18 @@ def default_sched():
         # qkv / proj / fc1 / fc2 at 65536 rows +3.3 / +3 / +4 / +1 %)
         "store_policy": " nt",
     }
+
+
+def m16_sched(base=None):
+    """the 16x16x32 schedule of the same tile: slot = index of the MFMA (0..127, 16 cycles each) a side instruction is emitted behind.
+    One DMA piece per 5 slots = 80 cycles (the 2.5 32-cycle slots of the form above), each alone in its gap, its m0 in the gap before."""
+    dma = [41 + 5 * p for p in range(16)]
+    busy = set(dma) | set(d - 1 for d in dma)
+    free = [s for s in range(93, 128) if s not in busy]
+    return dict(base or default_sched(), mfma="16x16x32",
+                rd1=[1 + 2 * i for i in range(16)],      # k-step 1's reads: every second gap of the first 32
+                tog1=(32, 35), pre_slot=33, barA=36, dma=dma, barB=92,
+                rd0=free[:16], adv=free[16])             # the next K-tile's k-step 0 in the free gaps behind barrier B, then the nine SALU of the advance
 
 
 def experiment_scheds():
@@ -1070,7 +1323,12 @@ def variants():
     out += [("psam_gemm_asm_f32_sk", EPI_F32, dict(keep, splitk=True))]
     ln = dict(base, ln_cons=True, ln_prod=True, store16_policy=" nt")
     out += [("psam_gemm_asm_f16_ln", EPI_F16, ln), ("psam_gemm_asm_gelu_ln", EPI_GELU_F16, ln), ("psam_gemm_asm_f32_ln", EPI_F32, ln)]
+    # the same tile on v_mfma_f32_16x16x32_f16 (csrc/gemm.hip tile 17): plain and folded-LayerNorm forms
+    out += [("psam_gemm_asm_f16_m16", EPI_F16, m16_sched(base)), ("psam_gemm_asm_gelu_m16", EPI_GELU_F16, m16_sched(base)), ("psam_gemm_asm_f32_m16", EPI_F32, m16_sched(base))]
+    out += [("psam_gemm_asm_f16_ln_m16", EPI_F16, m16_sched(ln)), ("psam_gemm_asm_gelu_ln_m16", EPI_GELU_F16, m16_sched(ln)), ("psam_gemm_asm_f32_ln_m16", EPI_F32, m16_sched(ln))]
     if "--experiments" in sys.argv:
+        for nm, epi in (("f16", EPI_F16), ("gelu", EPI_GELU_F16), ("f32", EPI_F32)):     # _m16_v1: the 16x16x32 schedule + trace
+            out.append(("psam_gemm_asm_%s_m16_v1" % nm, epi, m16_sched(dict(base, trace=True))))
         for i, sc in enumerate(experiment_scheds()):
             for nm, epi in (("f16", EPI_F16), ("gelu", EPI_GELU_F16), ("f32", EPI_F32)):
                 out.append(("psam_gemm_asm_%s_v%d" % (nm, i + 1), epi, sc))

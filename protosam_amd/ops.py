@@ -309,9 +309,17 @@ def gemm_set_tile(tile):
     _lib.check(_lib.lib().psam_gemm_set_tile(int(tile)), "psam_gemm_set_tile")
 
 
+def gemm_last_tile():
+    """The tile the most recent gemm() call was dispatched to, after every fallback (0 before the first call)."""
+    import ctypes
+    t = ctypes.c_int(0)
+    _lib.check(_lib.lib().psam_gemm_last_tile(ctypes.byref(t)), "psam_gemm_last_tile")
+    return t.value
+
+
 def gemm_set_option(name, value):
     """Dispatch switches of the GEMM: "asm", "half_tiles", "splitk", "nsplit" (0 / 1), "max_wgs" (cap on the persistent grids,
-    0 = none) (see include/protosam_hip.h)."""
+    0 = none), "mfma16" (0 / 1 / negative = the measured rule: tile 17 in place of tile 15) (see include/protosam_hip.h)."""
     _bump_dispatch()
     _lib.check(_lib.lib().psam_gemm_set_option(name.encode(), int(value)), "psam_gemm_set_option")
 
