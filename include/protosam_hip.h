@@ -76,7 +76,8 @@ int psam_gemm_f16_splitk_ln(const void* A, const void* W, const float* bias, flo
  * rounding of it, not bit-identical); a tile that cannot take the call's layout falls back (16 -> 15 -> 11 -> 1, 17 -> 11 -> 1). */
 int psam_gemm_set_tile(int tile);
 /* *tile = the tile the most recent psam_gemm_f16 / psam_gemm_f16_ln call of this process was dispatched to, after every fallback
- * (0 before the first call): what tests and A/B tools check a forced tile against. */
+ * (0 before the first call): what tests and A/B tools check a forced tile against. 12 (four-deep ring) and 13 (64x64) are reported
+ * whenever those kernels ran, forced or chosen for a small launch; a forced 12 / 13 that cannot take the call reports 1. */
 int psam_gemm_last_tile(int* tile);
 /* Schedule variant of the assembly GEMM (tile 15): 0 = the shipped kernels; n > 0 selects the numbered experiment kernels of a
  * library built with `make GENFLAGS=--experiments` (csrc/gemm_asm_gen.py; a missing variant makes the next GEMM return an error). */

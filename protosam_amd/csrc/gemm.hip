@@ -1821,7 +1821,7 @@ static int gemm_dispatch(const void* A, const void* W, const float* bias, void* 
       if (seen[key]++ == 0) fprintf(stderr, "psam_gemm_f16: %s\n", key);
     }
   }
-  g_last_tile = tsel;
+  g_last_tile = tsel;   // (the 64x64 and deep-ring choices below record themselves: psam_gemm_last_tile names the kernel that ran)
   if (tsel == 15) return launch_asm(p, epilogue, s);
   if (tsel == 16) return launch_asm(p, epilogue, s, 2);
   if (tsel == 17) return launch_asm(p, epilogue, s, 3);
@@ -1861,6 +1861,7 @@ static int gemm_dispatch(const void* A, const void* W, const float* bias, void* 
   // (its epilogue has no head-major plane addressing: psam_gemm_f16_heads stays on the 128-tile kernel)
   if ((tsel == 13 || (tsel == 1 && g_tile_override <= 0 && gemm_option(OPT_SMALL) && (int)grid.x * 2 <= num_cus())) && !lnf && !head_hd && K >= 64 &&
       epilogue != EPI_RELU_F16 && (epilogue == EPI_F32 || (ldo % 4) == 0)) {
+    g_last_tile = 13;
     switch (epilogue) {
       case EPI_F16: launch_s64<EPI_F16>(p, s); break;
       case EPI_GELU_F16: launch_s64<EPI_GELU_F16>(p, s); break;
@@ -1868,11 +1869,12 @@ static int gemm_dispatch(const void* A, const void* W, const float* bias, void* 
     }
     return psam_launch_status();
   }
-  if (tsel == 13) tsel = 1;
+  if (tsel == 13) g_last_tile = tsel = 1;   // (a forced 13 that cannot be taken: head-major, folded LayerNorm, ldo % 4)
   // tile 12: the 128x128 kernel with a four-deep K-tile ring where a launch leaves at most one workgroup per CU (gemm_f16_deep_kernel;
   // bit-identical to tile 1). PSAM_GEMM_DEEP=0 / psam_gemm_set_option("deep", 0) keeps tile 1; psam_gemm_set_tile(12) forces it.
   if ((tsel == 12 || (tsel == 1 && g_tile_override <= 0 && gemm_option(OPT_DEEP) && (int)grid.x <= num_cus())) && !lnf && K >= 256 &&
       epilogue != EPI_RELU_F16) {
+    g_last_tile = 12;
     switch (epilogue) {
       case EPI_F16: launch_deep<EPI_F16>(p, grid, s); break;
       case EPI_GELU_F16: launch_deep<EPI_GELU_F16>(p, grid, s); break;
@@ -1880,7 +1882,7 @@ static int gemm_dispatch(const void* A, const void* W, const float* bias, void* 
     }
     return psam_launch_status();
   }
-  if (tsel == 12) tsel = 1;
+  if (tsel == 12) g_last_tile = tsel = 1;   // (a forced 12 below its four K-tiles, or with a folded LayerNorm)
   if (tsel == 11) {
     if (lnf) {   // separate instantiations: the plain kernels stay as they were
       if (epilogue == EPI_F16) launch8kp<EPI_F16, true>(p, s);

@@ -15,56 +15,10 @@ The bound is derived, not tuned (u = 2^-24, the unit roundoff of fp32):
 Tile 17 against tile 15 on the same inputs: within twice the bound (both are inside it; they are not bit-identical - the two MFMA
 shapes sum in different orders). A test without a GPU evaluates the same expressions in fp32 on the CPU through the same assertions.
 Run with -s for the worst error / bound ratio of every case."""
-import math
-
 import pytest
 import torch
 
-U = 2.0 ** -24
-H = 2.0 ** -11
-
-
-def _rand(shape, dev, scale, seed):
-    g = torch.Generator(device="cpu").manual_seed(seed)
-    return (torch.randn(shape, generator=g) * scale).to(dev)
-
-
-def _gamma(k):
-    return k * U / (1.0 - k * U)
-
-
-def _gelu64(x):
-    return 0.5 * x * (1.0 + torch.erf(x / math.sqrt(2.0)))
-
-
-class Case:
-    """float64 reference and bound of out = epilogue(a w^T + bias) for fp16 a [M, K], w [N, K]"""
-
-    def __init__(self, a, w, bias, epi, resid=None, gamma=None, resid_mod=0):
-        a64, w64 = a.double().cpu(), w.double().cpu()
-        K = a.shape[1]
-        acc = a64 @ w64.t()
-        e_acc = _gamma(K) * (a64.abs() @ w64.abs().t())
-        v = acc + bias.double().cpu()
-        if epi == 0:
-            self.ref, self.bound = v, e_acc + H * v.abs()
-        elif epi == 1:
-            self.ref = _gelu64(v)
-            self.bound = 1.13 * e_acc + 3.4e-6 + H * self.ref.abs()
-        else:
-            r = resid.double().cpu()
-            if resid_mod:
-                r = r[torch.arange(a.shape[0]) % resid_mod]
-            g = gamma.double().cpu() if gamma is not None else torch.ones(w.shape[0], dtype=torch.float64)
-            self.ref = r + g * v
-            self.bound = g.abs() * e_acc + 3 * U * (r.abs() + g.abs() * v.abs())
-
-    def check(self, out, what, scale=1.0):
-        d = (out.double().cpu() - self.ref).abs()
-        ratio = (d / (scale * self.bound)).max().item()
-        print(f"{what}: worst |error| / bound = {ratio:.3f} (max |error| {d.max().item():.3e})")
-        assert torch.isfinite(out).all() and ratio <= 1.0, (what, ratio)
-        return ratio
+from oracle.gemm import Case, _gamma, _ln_reference, _rand      # the float64 references and bounds, shared with tests/test_gemm_exact_gpu.py
 
 
 def _within_twice(o17, o15, case, what):
@@ -157,22 +111,6 @@ def test_tile17_residual_table(dev):
             ops.gemm_set_tile(0)
     case.check(outs[0], "tile 17 resid_mod 256")
     _within_twice(outs[0], outs[1], case, "resid_mod 256")
-
-
-def _ln_reference(x16, wf, t, mr2, s, act):
-    """float64 y = act(rstd (x16 W'^T - mean s) + t) and its bound (module docstring) on the consumer's own inputs"""
-    x64, w64 = x16.double().cpu(), wf.double().cpu()
-    K = x16.shape[1]
-    mean, rstd = mr2[:, 0].double().cpu()[:, None], mr2[:, 1].double().cpu()[:, None]
-    s64 = s.double().cpu()[None, :]
-    ms = (mean * s64).abs()
-    e_c = _gamma(K + 3) * (x64.abs() @ w64.abs().t() + ms) + 3 * 2.0 ** -22 * ms + 2.0 ** -25 * (mean.abs() + s64.abs())
-    v = rstd * (x64 @ w64.t() - mean * s64) + t.double().cpu()
-    e_v = rstd.abs() * e_c + U * v.abs()
-    if act:
-        ref = _gelu64(v)
-        return ref, 1.13 * e_v + 3.4e-6 + H * ref.abs()
-    return v, e_v + H * v.abs()
 
 
 @pytest.mark.gpu
