@@ -408,6 +408,22 @@ int psam_rotate_nearest(const float* src, float* dst, const float* xg, const flo
                         int crop_y, int crop_x, int outH, int outW, void* stream);
 int psam_resize_aa(const float* src, float* tmp, float* dst, int C, int H, int W, int OH, int OW, void* stream);
 
+/* Fused intake of n uint8 images of different sizes, packed in `src` (src_bytes long): resize to (oh, ow), (v - mean[c]) / std[c],
+ * zero padding to S x S -> out fp32 [n, C, S, S], one launch, no global scratch. dataloaders/PolypDataset.py:319-348 through
+ * models/segment_anything/utils/transforms.py:62-110 (mode 0) and predictor.py:47-58 through transforms.py:30-38 (mode 1).
+ * rows_host: n rows of 5 int64 in HOST memory: byte offset of the image in src, H, W, oh, ow ((oh, ow) = get_preprocess_shape(H, W,
+ *   S) for the reference's use; any 1 <= oh, ow <= S is served). They are checked here and copied to rows_dev (n * 5 int64 of DEVICE
+ *   memory), the table the kernel reads.
+ * C = 3: interleaved [H, W, 3] images; C = 1: [H, W] planes (normalised with mean3[0] / std3[0]).
+ * mode 0: aten _upsample_bilinear2d_aa in fp32, bit-identical to uint8 -> float, psam_resize_aa, psam_normalize_chw, pad.
+ *   threshold = 1 (C = 1, mode 0 only; mean3 / std3 may be NULL): v > 0.5f ? 1 : 0 instead of the normalisation.
+ * mode 1: Pillow's Image.resize((ow, oh), BILINEAR) of the uint8 image, exactly, then the normalisation of the uint8 value.
+ * mean3 / std3 are HOST pointers. Status 1, with `out` and rows_dev untouched: a null pointer, n outside [1, 65535], C not 1 or 3,
+ *   S outside [1, 16384], a bad mode / threshold combination, a source side outside [1, 8192], oh or ow outside [1, S], a source side
+ *   above 16 times its resized side, an image that does not lie inside [0, src_bytes). */
+int psam_image_intake(const void* src, long long src_bytes, const long long* rows_host, void* rows_dev, int n, int C, int S, int mode,
+                      int threshold, const float* mean3, const float* std3, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -80,6 +80,8 @@ SIGNATURES = {
     "psam_rotate_nearest": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
                             c_int, c_void_p],
     "psam_resize_aa": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p],
+    "psam_image_intake": [c_void_p, c_longlong, ctypes.POINTER(c_longlong), c_void_p, c_int, c_int, c_int, c_int, c_int,
+                          ctypes.POINTER(c_float), ctypes.POINTER(c_float), c_void_p, c_void_p],
     "psam_volume_stats": [c_void_p, c_int, ctypes.c_longlong, c_float, c_float, c_void_p, c_void_p],
     "psam_volume_slices": [c_void_p, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_int, c_int, c_int,
                            c_void_p, c_void_p],

@@ -77,3 +77,45 @@ __device__ __forceinline__ float up_sample(const float* __restrict__ p, int IN, 
   }
   return ly.l0 * (lx.l0 * a + lx.l1 * b) + ly.l1 * (lx.l0 * c + lx.l1 * d);
 }
+
+// Anti-aliased bilinear taps of one output index along one axis (aten UpSampleKernel.cpp,
+// `_compute_indices_min_size_weights_aa` with the triangle filter), shared by psam_resize_aa and psam_image_intake so that
+// the fused intake computes the bits of the unfused chain: scale = in / out, support = max(scale, 1), centre =
+// scale * (i + 0.5), taps [int(centre - support + 0.5), int(centre + support + 0.5)) clipped to the input, weights
+// triangle((j - centre + 0.5) / max(scale, 1)) normalised to sum 1. All fp32, one rounding per written operation.
+struct AaTap {
+  int xmin, xsize;
+  float center, invscale, total;
+};
+__device__ __forceinline__ AaTap aa_tap(int i, int in_len, int out_len) {
+  const float scale = (float)in_len / (float)out_len;
+  const float support = scale >= 1.f ? scale : 1.f;
+  AaTap t;
+  t.invscale = scale >= 1.f ? 1.f / scale : 1.f;
+  t.center = scale * ((float)i + 0.5f);
+  int xmin = (int)(t.center - support + 0.5f);
+  xmin = xmin > 0 ? xmin : 0;
+  int xmax = (int)(t.center + support + 0.5f);
+  xmax = xmax < in_len ? xmax : in_len;
+  t.xmin = xmin;
+  t.xsize = xmax - xmin;
+  float total = 0.f;
+  for (int j = 0; j < t.xsize; ++j) {
+    float a = fabsf(((float)(j + xmin) - t.center + 0.5f) * t.invscale);
+    total += a < 1.f ? 1.f - a : 0.f;
+  }
+  t.total = total;
+  return t;
+}
+__device__ __forceinline__ float aa_weight(const AaTap& t, int j) {
+  float a = fabsf(((float)(j + t.xmin) - t.center + 0.5f) * t.invscale);
+  float w = a < 1.f ? 1.f - a : 0.f;
+  if (t.total != 0.f) w /= t.total;
+  return w;
+}
+// acc + w * v as one fused multiply-add (what the compiler made of `acc += w * v` in resize_aa_pass_kernel; spelled out so
+// that every kernel that accumulates taps rounds alike whatever the contraction setting)
+__device__ __forceinline__ float aa_mac(float acc, float w, float v) { return fmaf(w, v, acc); }
+
+// Sam.preprocess normalisation of one value (modeling/sam.py:163-168), shared by psam_normalize_chw and psam_image_intake
+__device__ __forceinline__ float norm_px(float v, float mean, float sd) { return (v - mean) / sd; }

@@ -407,7 +407,7 @@ __global__ void normalize_chw_kernel(const void* __restrict__ x, int in_u8, size
   const float v = in_u8 ? (float)reinterpret_cast<const uint8_t*>(x)[i] : reinterpret_cast<const float*>(x)[i];
   const float mean = c == 0 ? m0 : (c == 1 ? m1 : m2);
   const float sd = c == 0 ? s0 : (c == 1 ? s1 : s2);
-  y[i] = (v - mean) / sd;
+  y[i] = norm_px(v, mean, sd);
 }
 extern "C" int psam_normalize_chw(const void* x, int in_u8, int B, long long plane, const float* mean3,
                                   const float* std3, float* y, void* stream) {
@@ -659,28 +659,10 @@ __global__ void resize_aa_pass_kernel(const float* __restrict__ src, float* __re
   // one thread per (output index i along the resized axis, line l along the other axis); blockIdx.z = plane
   const int i = blockIdx.x * blockDim.x + threadIdx.x, l = blockIdx.y;
   if (i >= out_len || l >= lines) return;
-  const float scale = (float)in_len / (float)out_len;
-  const float support = scale >= 1.f ? scale : 1.f;
-  const float invscale = scale >= 1.f ? 1.f / scale : 1.f;
-  const float center = scale * ((float)i + 0.5f);
-  int xmin = (int)(center - support + 0.5f);
-  xmin = xmin > 0 ? xmin : 0;
-  int xmax = (int)(center + support + 0.5f);
-  xmax = xmax < in_len ? xmax : in_len;
-  const int xsize = xmax - xmin;
+  const AaTap t = aa_tap(i, in_len, out_len);
   const float* s = src + blockIdx.z * plane_in + (size_t)l * line_in_stride;
-  float total = 0.f;
-  for (int j = 0; j < xsize; ++j) {
-    float a = fabsf(((float)(j + xmin) - center + 0.5f) * invscale);
-    total += a < 1.f ? 1.f - a : 0.f;
-  }
   float acc = 0.f;
-  for (int j = 0; j < xsize; ++j) {
-    float a = fabsf(((float)(j + xmin) - center + 0.5f) * invscale);
-    float w = a < 1.f ? 1.f - a : 0.f;
-    if (total != 0.f) w /= total;
-    acc += w * s[(size_t)(j + xmin) * in_stride];
-  }
+  for (int j = 0; j < t.xsize; ++j) acc = aa_mac(acc, aa_weight(t, j), s[(size_t)(j + t.xmin) * in_stride]);
   dst[blockIdx.z * plane_out + (size_t)l * line_out_stride + (size_t)i * out_stride] = acc;
 }
 extern "C" int psam_resize_aa(const float* src, float* tmp, float* dst, int C, int H, int W, int OH, int OW, void* stream) {

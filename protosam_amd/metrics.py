@@ -77,6 +77,35 @@ def calc_iou(boxA, boxB):
     return inter / float(boxA[2] * boxA[3] + boxB[2] * boxB[3] - inter)
 
 
+def eval_detection(pred_list, as_frame=None):
+    """validation_protosam.py:81-122: the detection table of a list of {"pred_bbox", "gt_bbox", "score"} with (x, y, w, h) boxes (as
+    `score_slices` returns under "bboxes_w_scores"). Per IoU threshold of np.round(np.arange(0.5, 1.0, 0.05), 2): a prediction is a
+    true positive when calc_iou(pred_bbox, gt_bbox) >= threshold, else a false positive; precision = tp / (tp + fp), recall =
+    tp / len(pred_list), f1 = 2 p r / (p + r) - nan where that expression is 0 / 0 (no true positive; the reference's Python floats raise there, and the rows
+    of the other thresholds are still wanted).
+    An empty list divides by zero and two empty boxes make calc_iou divide by zero, as in the reference: both raise.
+    -> a pandas DataFrame (the reference's return) where pandas imports, else the list of row dicts; as_frame=False / True forces
+    either."""
+    rows = []
+    for thr in np.round(np.arange(0.5, 1.0, 0.05), 2):
+        tp = sum(1 for p in pred_list if calc_iou(p["pred_bbox"], p["gt_bbox"]) >= thr)
+        fp = len(pred_list) - tp
+        precision = tp / (tp + fp)
+        recall = tp / len(pred_list)
+        f1 = 2 * (precision * recall) / (precision + recall) if precision + recall > 0 else float("nan")
+        rows.append({"iou_threshold": thr, "tp": tp, "fp": fp, "n_gt": len(pred_list), "f1": f1, "precision": precision,
+                     "recall": recall})
+    if as_frame is False:
+        return rows
+    try:
+        import pandas as pd
+    except ImportError:
+        if as_frame:
+            raise
+        return rows
+    return pd.DataFrame(rows)
+
+
 def score_slices(counts, scores=None, cases=None, skip_no_organ_slices=True):
     """The numbers of the per-slice loop of validation_protosam.py:369-448 from a counts table [n, 12] (host side, float64).
     Per row dice / iou / precision / recall with the 1e-8 guards (:169-185). A row whose ground truth is empty (tp + fn == 0) is

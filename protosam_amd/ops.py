@@ -1291,6 +1291,72 @@ def normalize_chw(x, mean3, std3, out=None):
 
 
 
+INTAKE_MAX_SIDE, INTAKE_MAX_SCALE = 8192, 16        # the size range of psam_image_intake (csrc/intake.hip)
+
+
+def intake_shape(h, w, S):
+    """(oh, ow) of an [h, w] image resized so that its long side is S: `ResizeLongestSide.get_preprocess_shape`."""
+    scale = S * 1.0 / max(h, w)
+    return (int(h * scale + 0.5), int(w * scale + 0.5))
+
+
+def intake_supported(h, w, S):
+    """whether psam_image_intake serves an [h, w] source at model size S (sides 1..8192, at most 16 source pixels per resized one)"""
+    if not (1 <= h <= INTAKE_MAX_SIDE and 1 <= w <= INTAKE_MAX_SIDE and S >= 1):
+        return False
+    oh, ow = intake_shape(h, w, S)
+    return 1 <= oh <= S and 1 <= ow <= S and h <= INTAKE_MAX_SCALE * oh and w <= INTAKE_MAX_SCALE * ow
+
+
+def image_intake_packed(buf, rows, C, S, mode, mean3, std3, threshold=False, out=None):
+    """psam_image_intake on images already packed in the uint8 device buffer `buf`; rows: per image (byte offset, H, W, oh, ow).
+    -> out fp32 [n, C, S, S]."""
+    import ctypes
+    _req(buf, torch.uint8, "buf")
+    assert buf.is_contiguous() and buf.dim() == 1
+    n = len(rows)
+    flat = [int(v) for r in rows for v in r]
+    assert len(flat) == 5 * n
+    rows_host = (ctypes.c_longlong * max(len(flat), 1))(*flat)
+    rows_dev = torch.empty((max(n, 1), 5), dtype=torch.int64, device=buf.device)
+    if out is None:
+        out = torch.empty((n, C, max(S, 0), max(S, 0)), dtype=torch.float32, device=buf.device)
+    _req(out, torch.float32, "out")
+    assert out.is_contiguous() and out.numel() >= n * C * max(S, 0) * max(S, 0)
+    m = None if mean3 is None else (ctypes.c_float * 3)(*[float(v) for v in mean3])
+    sd = None if std3 is None else (ctypes.c_float * 3)(*[float(v) for v in std3])
+    st = _lib.lib().psam_image_intake(_ptr(buf), buf.numel(), rows_host, _ptr(rows_dev), n, C, S, int(mode), 1 if threshold else 0,
+                                     m, sd, _ptr(out), _stream())
+    _lib.check(st, "psam_image_intake")
+    return out
+
+
+def image_intake(images, S, mode, mean3, std3, threshold=False, out=None):
+    """Resize + normalise + zero-pad a list of uint8 device images of any sizes in one launch (psam_image_intake).
+    images: uint8 device tensors, all [H, W, 3] (interleaved RGB) or all [H, W]. Each is resized to (oh, ow) =
+    get_preprocess_shape(H, W, S). mode 0: aten antialiased bilinear (bit-identical to float -> resize_aa -> normalize_chw -> pad);
+    mode 1: Pillow's BILINEAR resize of the uint8 image, exactly. threshold (masks, mode 0): v > 0.5 ? 1 : 0 instead of the
+    normalisation. -> (out fp32 [n, C, S, S], [(oh, ow)])."""
+    if not images:
+        raise ValueError("images: expected at least one image")
+    C = 3 if images[0].dim() == 3 else 1
+    rows, sizes, flat, off = [], [], [], 0
+    for k, im in enumerate(images):
+        _req(im, torch.uint8, f"images[{k}]")
+        if (im.dim() == 3 and im.shape[2] == 3) != (C == 3) or im.dim() not in (2, 3):
+            raise ValueError(f"images[{k}]: expected {'[H, W, 3]' if C == 3 else '[H, W]'}, got {tuple(im.shape)}")
+        h, w = int(im.shape[0]), int(im.shape[1])
+        oh, ow = intake_shape(h, w, S) if h > 0 and w > 0 and S > 0 else (0, 0)
+        rows.append((off, h, w, oh, ow))
+        sizes.append((oh, ow))
+        flat.append(im.contiguous().reshape(-1))
+        off += h * w * C
+    buf = flat[0] if len(flat) == 1 else torch.cat(flat)
+    if buf.numel() == 0:
+        buf = torch.zeros((1,), dtype=torch.uint8, device=images[0].device)        # (an empty image: the launcher refuses its row)
+    return image_intake_packed(buf, rows, C, S, mode, mean3, std3, threshold, out), sizes
+
+
 # ---- HIP graph replay of a launch-only forward -------------------------------------------------------------------
 def graph_wanted(x, max_batch_rows):
     """PSAM_HIPGRAPH = auto (default: small calls only) / 1 / 0. Never while per-kernel timers are attached (they need the launches

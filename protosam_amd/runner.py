@@ -304,6 +304,72 @@ def evaluate_slices_class_supports(model, vol, labels, supports, part_table, zs,
     return table, _slices_class_supports_loop(model, vol, supports, part_table, zs, batch, keep, buf, sink)
 
 
+# ---- image sets (image_io.ImageSet): the polyp branch of validation_protosam.py:307-449 -----------------------------------------
+@torch.no_grad()
+def run_images(model, image_set, support, indices, batch=4, out=None):
+    """Runs ProtoSAM on the images `indices` of `image_set`, `batch` at a time through `forward_batch` (a last short batch is
+    allowed). support: (images, masks) lists of [1,3,S,S] / [1,S,S] as `ImageSet.get_support` returns them; the support input is
+    built once, so its features stay cached as in `run_slices`. -> uint8 masks [len(indices), S, S], prompts per image and the
+    confidence lists per image."""
+    indices = list(indices)
+    if out is None:
+        out = torch.zeros((len(indices), image_set.S, image_set.S), dtype=torch.uint8, device=image_set.device)
+    stats, scores, _ = _images_loop(model, image_set, support, indices, batch, out, None, None)
+    return out, stats, scores
+
+
+def _images_loop(model, image_set, support, indices, batch, out, buf, sink):
+    """The loop of `run_images`; out / buf as `_slices_loop`; sink(i, j, masks, labels) gets each batch's masks and loaded labels.
+    -> prompts per image, confidences per image, case per image."""
+    S = image_set.S
+    stats, scores, cases = [0] * len(indices), [None] * len(indices), [None] * len(indices)
+    cin = None
+    for i in range(0, len(indices), max(int(batch), 1)):
+        j = min(i + max(int(batch), 1), len(indices))
+        q, labels, _, cs = image_set.load(indices[i:j])
+        if cin is None:
+            cin = InputFactory.create_input(TYPE_ALPNET, q, support_images=list(support[0]), support_labels=list(support[1]),
+                                            isval=True, val_wsize=2)
+        res = model.forward_batch(q, cin)
+        st = model.last_stats.get("per_slice", [model.last_stats])
+        dst = _batch_dst(out, buf, i, j)
+        for k, (pred, sc) in enumerate(res):
+            if pred.shape[-1] == S:
+                dst[k].copy_(pred)
+            else:                                 # empty coarse mask: the all-zero 1024 x 1024 arg-max map (ProtoSAM.py:612-613)
+                dst[k].zero_()
+            stats[i + k] = st[k].get("n_prompts", 0) if k < len(st) else 0
+            scores[i + k] = sc
+            cases[i + k] = cs[k]
+        if sink is not None:
+            sink(i, j, dst, labels)
+    return stats, scores, cases
+
+
+@torch.no_grad()
+def evaluate_images(model, image_set, support, indices, batch=4, keep=None, skip_no_organ_slices=True):
+    """`run_images` scored where each batch lies: one `ops.seg_counts` per batch against the batch's own labels, then
+    `metrics.score_slices` on the table with the per-image confidences and cases. -> its dict (dice / iou / precision / recall, their
+    means, per-case means, "bboxes_w_scores" for `metrics.eval_detection`) plus "table" (int64 [n, 12], host) and "n_prompts".
+    keep= (uint8 [len(indices), S, S]) also receives the masks."""
+    from . import ops
+    from .metrics import score_slices
+    indices = list(indices)
+    S, dev = image_set.S, image_set.device
+    table = torch.empty((len(indices), 12), dtype=torch.int64, device=dev)
+    if keep is not None:
+        assert tuple(keep.shape) == (len(indices), S, S) and keep.dtype == torch.uint8 and keep.is_contiguous()
+    buf = None if keep is not None else torch.empty((min(max(int(batch), 1), len(indices)), S, S), dtype=torch.uint8, device=dev)
+
+    def sink(i, j, masks, labels):
+        ops.seg_counts(masks, labels, class_rows(j - i).tolist(), out=table[i:j])
+    stats, scores, cases = _images_loop(model, image_set, support, indices, batch, keep, buf, sink)
+    host = table.cpu().numpy()
+    res = score_slices(host, scores=scores, cases=cases, skip_no_organ_slices=skip_no_organ_slices)
+    res["table"], res["n_prompts"] = host, stats
+    return res
+
+
 def gather_counts(local, world):
     """One all-gather of the per-rank int64 counts tables [k, 12] -> [world*k, 12] (rank-major; `interleave_rank_major` puts the
     rows back in z order): 96 bytes per (slice, class) cross the link instead of an S*S mask."""

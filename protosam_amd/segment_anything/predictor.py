@@ -3,11 +3,14 @@
 Same methods, arguments, return types (numpy from `predict`, tensors from `predict_torch`) and the same RuntimeError
 when predicting before `set_image`. ProtoSAM hands over 1024x1024 images (models/ProtoSAM.py:592-594,651-660), for
 which `apply_image`, the padding and the second post-processing resize are identities; other sizes take the reference's
-route: PIL resize on the host, zero padding after normalisation, crop + resize of the mask logits.
+route: PIL's bilinear resize, zero padding after normalisation, crop + resize of the mask logits. `set_image` does the first
+two on the device: the uint8 image is uploaded once and `ops.image_intake` (mode 1: Pillow's 8-bit resampling, exactly) writes
+the normalised, padded encoder input; images outside that kernel's size range keep the host resize.
 """
 import numpy as np
 import torch
 
+from .. import ops
 from .utils.transforms import ResizeLongestSide
 
 
@@ -21,10 +24,27 @@ class SamPredictor:
         assert image_format in ["RGB", "BGR"], f"image_format must be in ['RGB', 'BGR'], is {image_format}."
         if image_format != self.model.image_format:
             image = image[..., ::-1]
+        S = self.model.image_encoder.img_size
+        if image.dtype == np.uint8 and image.ndim == 3 and image.shape[2] == 3 and ops.intake_supported(image.shape[0], image.shape[1], S):
+            self._set_image_device(np.ascontiguousarray(image), S)
+            return
         input_image = self.transform.apply_image(image)
         t = torch.as_tensor(np.ascontiguousarray(input_image), device=self.device)
         t = t.permute(2, 0, 1).contiguous()[None, :, :, :]
         self.set_torch_image(t, image.shape[:2])
+
+    @torch.no_grad()
+    def _set_image_device(self, image, S):
+        """`apply_image` + `set_torch_image` with the resize, normalisation and padding in one kernel"""
+        t = torch.as_tensor(image, device=self.device)
+        x, sizes = ops.image_intake([t], S, 1, self.model._mean_host, self.model._std_host)
+        self.reset_image()
+        self.original_size = image.shape[:2]
+        self.input_size = sizes[0]
+        self.features_tokens = self.model.image_encoder.forward_tokens(x).clone()
+        g = self.model.image_encoder.grid
+        self.features = self.features_tokens.view(1, g, g, -1).permute(0, 3, 1, 2)
+        self.is_image_set = True
 
     @torch.no_grad()
     def set_torch_image(self, transformed_image, original_image_size):

@@ -1,12 +1,14 @@
 """`ResizeLongestSide` (models/segment_anything/utils/transforms.py:17-148): coordinate / box scaling, the target shape
-rule and the numpy image resize. On the hot path every image is already 1024x1024 and resizing is the identity; other
-sizes go through PIL's bilinear resize on the host exactly as the reference does (`resize(to_pil_image(image), size)`
-is `PIL.Image.resize(size[::-1], BILINEAR)`, :38). The antialiased torch resize of `apply_image_torch` is only ever the
-identity for ProtoSAM and raises otherwise."""
+rule and the image resizes. On the hot path every image is already 1024x1024 and resizing is the identity; `apply_image` sends
+other sizes through PIL's bilinear resize on the host exactly as the reference does (`resize(to_pil_image(image), size)` is
+`PIL.Image.resize(size[::-1], BILINEAR)`, :38; `SamPredictor.set_image` does the same on the device, ops.image_intake mode 1).
+`apply_image_torch` is the antialiased torch resize (:62-92): device tensors go through `ops.resize_aa`, CPU tensors (host data
+loading, as the reference's dataset code calls it) through stock `F.interpolate(antialias=True)`."""
 from copy import deepcopy
 
 import numpy as np
 import torch
+import torch.nn.functional as F
 
 
 class ResizeLongestSide:
@@ -29,9 +31,19 @@ class ResizeLongestSide:
         return np.array(Image.fromarray(image).resize((target[1], target[0]), Image.BILINEAR))
 
     def apply_image_torch(self, image):
-        if self.get_preprocess_shape(image.shape[-2], image.shape[-1], self.target_length) != tuple(image.shape[-2:]):
-            raise NotImplementedError("antialiased resize of non-1024 images is outside the accelerated path")
-        return image
+        """transforms.py:62-92 for [H,W], [C,H,W] and [B,C,H,W] float tensors."""
+        target = self.get_preprocess_shape(image.shape[-2], image.shape[-1], self.target_length)
+        if target == tuple(image.shape[-2:]):
+            return image
+        if image.dim() not in (2, 3, 4):
+            raise ValueError(f"apply_image_torch expects [H,W], [C,H,W] or [B,C,H,W], got {tuple(image.shape)}")
+        x = image[(None,) * (4 - image.dim())]
+        if image.is_cuda:
+            from ... import ops
+            y = ops.resize_aa(x.float().contiguous(), target[0], target[1])
+        else:
+            y = F.interpolate(x, target, mode="bilinear", align_corners=False, antialias=True)
+        return y.reshape(tuple(image.shape[:-2]) + target)
 
     def apply_coords(self, coords, original_size):
         old_h, old_w = original_size
@@ -56,11 +68,16 @@ class ResizeLongestSide:
         return self.apply_coords_torch(boxes.reshape(-1, 2, 2), original_size).reshape(-1, 4)
 
     def preprocess(self, x):
-        """Normalise + pad (transforms.py:94-110); with ProtoSAM's mean 0 / std 1 override this is the identity."""
+        """Normalise + zero-pad at the bottom and right (transforms.py:94-110); a 2-D input (a mask) is only padded."""
         if len(x.shape) != 2:
             dev = x.device
             x = (x - self.pixel_mean.to(dev)) / self.pixel_std.to(dev)
         h, w = x.shape[-2:]
-        if (h, w) != (self.target_length, self.target_length):
-            raise NotImplementedError("padding of non-square inputs is outside the accelerated path")
-        return x
+        S = self.target_length
+        if (h, w) == (S, S):
+            return x
+        if h > S or w > S:
+            raise ValueError(f"preprocess expects inputs with sides <= {S}, got {(h, w)}")
+        out = torch.zeros(tuple(x.shape[:-2]) + (S, S), dtype=x.dtype, device=x.device)    # F.pad(x, (0, padw, 0, padh))
+        out[..., :h, :w] = x
+        return out

@@ -182,3 +182,30 @@ def synth_pair_multi(size=1024, seed=0):
         imgs.append(torch.from_numpy(np.repeat(img[None, None], 3, axis=1).astype(np.float32)))
         masks.append(ms)
     return imgs[0], masks[0], imgs[1], masks[1]
+
+
+IMAGE_PAIR_SIZES = [(96, 128), (120, 90), (64, 64), (150, 100), (80, 144), (110, 77)]
+
+
+def write_image_pairs(root, n, seed=0, sizes=IMAGE_PAIR_SIZES):
+    """n seeded RGB PNG images with an elliptical bright region and their {0, 255} PNG masks, of mixed sizes (sizes[k % len]), under
+    root/images and root/masks -> (image_root, gt_root). Pillow writes them; PNG is lossless, so a reader gets these bytes back."""
+    import os
+    from PIL import Image
+    image_root, gt_root = os.path.join(root, "images"), os.path.join(root, "masks")
+    os.makedirs(image_root, exist_ok=True)
+    os.makedirs(gt_root, exist_ok=True)
+    rng = np.random.RandomState(seed + 4242)
+    for k in range(n):
+        h, w = sizes[k % len(sizes)]
+        yy, xx = np.mgrid[0:h, 0:w].astype(np.float32)
+        cy, cx = h * rng.uniform(0.4, 0.6), w * rng.uniform(0.4, 0.6)
+        ry, rx = h * rng.uniform(0.15, 0.25), w * rng.uniform(0.15, 0.25)
+        m = (((yy - cy) / ry) ** 2 + ((xx - cx) / rx) ** 2 <= 1.0)
+        f = _smooth_field(max(h, w), seed + k)[:h, :w]
+        base = 0.6 * f + 1.5 * m + 0.05 * rng.randn(h, w).astype(np.float32)
+        base = (base - base.min()) / max(float(base.max() - base.min()), 1e-6)
+        rgb = np.stack([base * g for g in (1.0, 0.8, 0.7)], -1)
+        Image.fromarray((rgb * 255).astype(np.uint8)).save(os.path.join(image_root, f"img_{k:03d}.png"))
+        Image.fromarray((m * 255).astype(np.uint8)).save(os.path.join(gt_root, f"img_{k:03d}.png"))
+    return image_root, gt_root
