@@ -247,12 +247,23 @@ int psam_small_linear_splitk(const float* x, const float* W, const float* b, con
 /* softmax(q k^T / sqrt(hd)) v with <= 16 keys (token self-attention; image->token attention). transformer.py:151-182 */
 int psam_small_attention(const void* q, const float* k, const float* v, void* out, int B, int Tq, int Tk, int NH, int hd,
                          int ldq, int ldk, int ldv, int ldo, int q_f16, void* stream);
-/* token -> image cross attention over Nk <= 4096 keys; K, V fp32 (kv_f32 = 1) or half.  transformer.py:163-167, 98-103 */
+/* Tokens per prompt set (5 output tokens + sparse prompts: 251 points, or a box and 249 points) up to which the decoder's token
+ * kernels run (csrc/common.h carries the same definition). The Python layers refuse more: ops.MAX_PROMPT_TOKENS is the same number. */
+#define PSAM_MAX_PROMPT_TOKENS 256
+/* psam_small_attention for 1 <= Tk <= PSAM_MAX_PROMPT_TOKENS keys, same arguments and strides: the keys in chunks of 16 staged in
+ * LDS once per workgroup (256 (query row, head) threads of one prompt set), chunk-local softmax sums merged online. hd 32 with
+ * fp32 q / out (token self-attention) or hd 16 with fp32 or fp16 q / out (image -> token). NH <= 8; k / v 16-byte aligned and
+ * ldk, ldv multiples of 4. transformer.py:151-182,218-240 */
+int psam_token_attention(const void* q, const float* k, const float* v, void* out, int B, int Tq, int Tk, int NH, int hd,
+                         int ldq, int ldk, int ldv, int ldo, int q_f16, void* stream);
+/* token -> image cross attention over Nk <= 4096 keys; K, V fp32 (kv_f32 = 1) or half.  transformer.py:163-167, 98-103.
+ * 64 <= Nk and T <= PSAM_MAX_PROMPT_TOKENS: one wave per token, 16 tokens per workgroup; otherwise one workgroup per (token, head). */
 int psam_t2i_attention(const float* q, const void* K, const void* V, float* out, int B, int T, int Nk, int NH,
                        int kv_f32, void* stream);
 /* The same with the 4096 keys of every (prompt set, head) split over S workgroups (1 <= S <= 16; one slice at a time a launch is 8-16
  * workgroups of latency-bound waves otherwise) and a second small launch that merges the partial (max, sum, weighted values) in the
- * order of the split index: `part` fp32 scratch of >= B * NH * S * T * 18 elements. Same reference lines as psam_t2i_attention. */
+ * order of the split index: `part` fp32 scratch of >= B * NH * S * T * 18 elements, T <= PSAM_MAX_PROMPT_TOKENS, Nk >= 64. Same
+ * reference lines as psam_t2i_attention. */
 int psam_t2i_attention_split(const float* q, const void* K, const void* V, float* out, int B, int T, int Nk, int NH,
                              int kv_f32, int S, float* part, void* stream);
 /* out = (a [+ a2[m % a2_mod]]) w^T + bias [+ resid], all fp32 on the exact-fp32 MFMA: the decoder's projections of the

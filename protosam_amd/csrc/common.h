@@ -16,6 +16,9 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 #define WAVE 64
 
+// tokens per prompt set the decoder's token kernels take (include/protosam_hip.h and ops.MAX_PROMPT_TOKENS carry the same number)
+#define PSAM_MAX_PROMPT_TOKENS 256
+
 static inline int psam_launch_status() {
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? PSAM_OK : PSAM_ERR_LAUNCH;

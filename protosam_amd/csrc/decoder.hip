@@ -594,6 +594,116 @@ extern "C" int psam_small_attention(const void* q, const float* k, const float* 
 }
 
 // =====================================================================================================
+// token_attention: the same product for 17 ... PSAM_MAX_PROMPT_TOKENS keys (prompt sets of more than 11 points or boxes). One thread
+// per (query row, head) as above, 256 of ONE prompt set per workgroup (grid.y = prompt set), and the keys in chunks of 16: the
+// workgroup stages a chunk's K / V rows (all heads) in LDS with one 16-byte load per four columns - image-to-token attention has
+// 4096 x 8 threads per prompt set that all read the same T rows - and every thread runs small_attention's two passes over the chunk
+// (16 scores in registers, every index a compile-time constant), then merges the chunk's (max, sum, weighted values) into its running
+// ones: chains of 16 additions inside a chunk and of Tk / 16 across chunks, not of Tk.
+// LDS rows are [key][head][HD + 4]: the four pad floats put the eight heads' 16-byte reads of a wave in different banks
+// (head stride 36 or 20 dwords: 0 36 8 44 16 52 24 60 / 0 20 40 60 16 36 56 12 mod 64); lanes of one head read one address.
+// Compiler's resource summary for gfx950:  <32, float, float> 144 VGPR, 36864 B LDS, 0 scratch (3 waves / SIMD);  <16, float, float>
+// and <16, half, half> 96 VGPR, 20480 B LDS, 0 scratch (5 waves / SIMD).
+template <int HD, typename QT, typename OT>
+__global__ __launch_bounds__(256) void token_attention_kernel(const QT* __restrict__ q, const float* __restrict__ k,
+                                                              const float* __restrict__ v, OT* __restrict__ out, int Tq, int Tk,
+                                                              int NH, int ldq, int ldk, int ldv, int ldo) {
+  constexpr int CH = 16, NHM = 8, H4 = HD / 4, P4 = H4 + 1;      // keys per chunk, heads the LDS rows hold, float4 per head (padded)
+  __shared__ float4 ks[CH * NHM * P4], vs[CH * NHM * P4];
+  const int b = blockIdx.y, tid = threadIdx.x;
+  const int i = blockIdx.x * 256 + tid;
+  const bool active = i < Tq * NH;          // (the others stage and wait at the barriers with the rest)
+  const int h = i % NH;
+  const size_t row = (size_t)b * Tq + (active ? i / NH : 0);
+  float qv[HD];
+  {
+    const QT* qp = q + row * ldq + h * HD;
+#pragma unroll
+    for (int d = 0; d < HD; ++d) qv[d] = (float)qp[d];
+  }
+  const float inv = 1.0f / sqrtf((float)HD);
+  float m = -INFINITY, l = 0.f, o[HD];
+#pragma unroll
+  for (int d = 0; d < HD; ++d) o[d] = 0.f;
+  const int W4 = NH * H4;                   // float4 per key row
+  for (int c0 = 0; c0 < Tk; c0 += CH) {
+    const int n = min(CH, Tk - c0);         // rows past the prompt set's last key are neither read nor used
+    __syncthreads();
+    for (int e = tid; e < n * W4; e += 256) {
+      const int j = e / W4, c4 = e - j * W4, hh = c4 / H4, d4 = c4 - hh * H4;
+      const size_t g = (size_t)b * Tk + c0 + j;
+      ks[(j * NHM + hh) * P4 + d4] = *reinterpret_cast<const float4*>(k + g * ldk + 4 * c4);
+      vs[(j * NHM + hh) * P4 + d4] = *reinterpret_cast<const float4*>(v + g * ldv + 4 * c4);
+    }
+    __syncthreads();
+    float s[CH];
+    float mc = -INFINITY;
+#pragma unroll
+    for (int j = 0; j < CH; ++j) {
+      s[j] = -INFINITY;
+      if (j < n) {
+        const float4* kp = ks + (j * NHM + h) * P4;
+        float a = 0.f;
+#pragma unroll
+        for (int d = 0; d < H4; ++d) {
+          const float4 x = kp[d];
+          a += qv[4 * d] * x.x; a += qv[4 * d + 1] * x.y; a += qv[4 * d + 2] * x.z; a += qv[4 * d + 3] * x.w;
+        }
+        s[j] = a * inv;
+        mc = fmaxf(mc, s[j]);
+      }
+    }
+    float lc = 0.f, oc[HD];
+#pragma unroll
+    for (int d = 0; d < HD; ++d) oc[d] = 0.f;
+#pragma unroll
+    for (int j = 0; j < CH; ++j) {
+      if (j < n) {
+        const float p = expf(s[j] - mc);
+        lc += p;
+        const float4* vp = vs + (j * NHM + h) * P4;
+#pragma unroll
+        for (int d = 0; d < H4; ++d) {
+          const float4 x = vp[d];
+          oc[4 * d] += p * x.x; oc[4 * d + 1] += p * x.y; oc[4 * d + 2] += p * x.z; oc[4 * d + 3] += p * x.w;
+        }
+      }
+    }
+    const float mn = fmaxf(m, mc);
+    const float a1 = expf(m - mn), a2 = expf(mc - mn);      // first chunk: m = -inf, a1 = 0
+    l = l * a1 + lc * a2;
+#pragma unroll
+    for (int d = 0; d < HD; ++d) o[d] = o[d] * a1 + oc[d] * a2;
+    m = mn;
+  }
+  if (!active) return;
+  OT* op = out + row * ldo + h * HD;
+#pragma unroll
+  for (int d = 0; d < HD; ++d) op[d] = (OT)(o[d] / l);
+}
+
+// q_f16 as psam_small_attention. Any 1 <= Tk <= PSAM_MAX_PROMPT_TOKENS (the callers send Tk <= 16 to psam_small_attention).
+extern "C" int psam_token_attention(const void* q, const float* k, const float* v, void* out, int B, int Tq, int Tk,
+                                    int NH, int hd, int ldq, int ldk, int ldv, int ldo, int q_f16, void* stream) {
+  if (B <= 0 || B > 65535 || Tq <= 0 || Tk <= 0 || Tk > PSAM_MAX_PROMPT_TOKENS || NH <= 0 || NH > 8) return PSAM_ERR_ARG;
+  if (!((hd == 16) || (hd == 32 && !q_f16))) return PSAM_ERR_ARG;
+  if ((ldk % 4) || (ldv % 4) || (((uintptr_t)k | (uintptr_t)v) & 15)) return PSAM_ERR_ARG;      // 16-byte loads of K / V
+  if ((long long)Tq * NH > 0x7fffffffLL - 256) return PSAM_ERR_ARG;
+  dim3 grid((unsigned)((Tq * NH + 255) / 256), (unsigned)B), block(256);
+  hipStream_t s = (hipStream_t)stream;
+  if (hd == 16 && q_f16)
+    hipLaunchKernelGGL((token_attention_kernel<16, half_t, half_t>), grid, block, 0, s, (const half_t*)q, k, v,
+                       (half_t*)out, Tq, Tk, NH, ldq, ldk, ldv, ldo);
+  else if (hd == 16)
+    hipLaunchKernelGGL((token_attention_kernel<16, float, float>), grid, block, 0, s, (const float*)q, k, v,
+                       (float*)out, Tq, Tk, NH, ldq, ldk, ldv, ldo);
+  else
+    hipLaunchKernelGGL((token_attention_kernel<32, float, float>), grid, block, 0, s, (const float*)q, k, v,
+                       (float*)out, Tq, Tk, NH, ldq, ldk, ldv, ldo);
+  return psam_launch_status();
+}
+
+// =====================================================================================================
 // t2i_attention: token -> image cross attention (transformer.py:163-167, 98-103). q fp32 [B,T,NH*16];
 // K, V fp16 [B*Nk, NH*16] (outputs of the k_proj / v_proj GEMMs); out fp32 [B,T,NH*16].
 // One block per (t, head, b); 256 threads x up to 16 keys each; two passes over register-resident scores.
@@ -684,8 +794,8 @@ __global__ __launch_bounds__(256) void t2i_attention_kernel(const float* __restr
   }
 }
 
-// Round 5: ALL tokens of a (prompt set, head) in one workgroup, one WAVE per token - lane kl walks keys kl, kl + 64, ... with an online
-// softmax, the 64 lanes merge at the end (no LDS, no barrier). The kernel above gives every (token, head, prompt set) its own
+// Round 5: ALL tokens of a (prompt set, head) in one workgroup (16 per workgroup past 16 tokens: token groups in grid.z), one WAVE per
+// token - lane kl walks keys kl, kl + 64, ... with an online softmax, the 64 lanes merge at the end (no LDS, no barrier). The kernel above gives every (token, head, prompt set) its own
 // workgroup, each of which streams the head's whole K / V slices (512 KB): nine tokens read them nine times (1 GB through the L2
 // per launch at 27 prompt sets; 173-281 us for 113 MB of K / V); here the T waves of a workgroup share them in the CU's caches.
 // (A first form with sixteen key lanes per token - 256 serial keys per thread - was latency-bound at the old kernel's 221 us.)
@@ -695,14 +805,17 @@ __global__ __launch_bounds__(1024) void t2i_attention_all_kernel(const float* __
                                                                 int Nk, int NH, int head_major, int S,
                                                                 float* __restrict__ part) {
   constexpr int HD = 16;
-  const int h = blockIdx.x, b = blockIdx.y, z = blockIdx.z;
-  const int tid = threadIdx.x, t = tid >> 6, kl = tid & 63;
+  // blockIdx.z = token group * S + key range: 16 tokens (waves) per workgroup, ceil(T / 16) groups (one for T <= 16, the launch of
+  // rounds 5-6); the waves past the last token of the last group leave at once (no LDS, no barrier in this kernel)
+  const int h = blockIdx.x, b = blockIdx.y, z = blockIdx.z % S, tg = blockIdx.z / S;
+  const int tid = threadIdx.x, t = tg * 16 + (tid >> 6), kl = tid & 63;
   const int C = NH * HD;
   const bool active = t < T;
+  if (!active) return;
   const float inv = 1.0f / sqrtf((float)HD);
   float qv[HD];
   {
-    const float* qp = q + ((size_t)b * T + (active ? t : 0)) * C + h * HD;
+    const float* qp = q + ((size_t)b * T + t) * C + h * HD;
 #pragma unroll
     for (int d = 0; d < HD; ++d) qv[d] = qp[d] * inv;
   }
@@ -804,7 +917,7 @@ extern "C" int psam_t2i_attention(const float* q, const void* K, const void* V, 
 // partials in the order of the split index: `part` fp32 scratch of at least B * NH * S * T * 18 elements.
 extern "C" int psam_t2i_attention_split(const float* q, const void* K, const void* V, float* out, int B, int T, int Nk, int NH,
                                         int kv_f32, int S, float* part, void* stream) {
-  if (S < 1 || S > 16 || T > 16 || Nk < 64 || (S > 1 && !part)) return PSAM_ERR_ARG;
+  if (S < 1 || S > 16 || T > PSAM_MAX_PROMPT_TOKENS || Nk < 64 || (S > 1 && !part)) return PSAM_ERR_ARG;
   return t2i_launch(q, K, V, out, B, T, Nk, NH, kv_f32, S, part, stream);
 }
 static int t2i_launch(const float* q, const void* K, const void* V, float* out, int B, int T, int Nk, int NH, int kv_f32, int S,
@@ -812,14 +925,15 @@ static int t2i_launch(const float* q, const void* K, const void* V, float* out, 
   if (B <= 0 || T <= 0 || Nk <= 0 || Nk > 4096) return PSAM_ERR_ARG;
   const int head_major = (kv_f32 >> 1) & 1;      // bit 1: K / V head-major [B][NH][Nk][16] (psam_gemm_f32_heads)
   kv_f32 &= 1;
-  if (head_major && !(T <= 16 && Nk >= 64)) return PSAM_ERR_ARG;
+  if (head_major && !(T <= PSAM_MAX_PROMPT_TOKENS && Nk >= 64)) return PSAM_ERR_ARG;
   static const int all_tokens = [] { const char* e = getenv("PSAM_T2I_ALL"); return e ? atoi(e) : 1; }();      // (0: the round-1 kernel, A/B)
-  if ((all_tokens || head_major || S > 1) && T <= 16 && Nk >= 64) {
+  if ((all_tokens || head_major || S > 1) && T <= PSAM_MAX_PROMPT_TOKENS && Nk >= 64) {
+    const dim3 grid(NH, B, S * ((T + 15) / 16)), block(64 * (T < 16 ? T : 16));     // (T <= 16: (NH, B, S) x 64 T, as before the groups)
     if (kv_f32)
-      hipLaunchKernelGGL(t2i_attention_all_kernel<float>, dim3(NH, B, S), dim3(64 * T), 0, (hipStream_t)stream, q, (const float*)K,
+      hipLaunchKernelGGL(t2i_attention_all_kernel<float>, grid, block, 0, (hipStream_t)stream, q, (const float*)K,
                          (const float*)V, out, T, Nk, NH, head_major, S, part);
     else
-      hipLaunchKernelGGL(t2i_attention_all_kernel<half_t>, dim3(NH, B, S), dim3(64 * T), 0, (hipStream_t)stream, q, (const half_t*)K,
+      hipLaunchKernelGGL(t2i_attention_all_kernel<half_t>, grid, block, 0, (hipStream_t)stream, q, (const half_t*)K,
                          (const half_t*)V, out, T, Nk, NH, head_major, S, part);
     if (S > 1)
       hipLaunchKernelGGL(t2i_combine_kernel, dim3((B * NH * T + 3) / 4), dim3(256), 0, (hipStream_t)stream, part, out, B, T, NH, S);

@@ -905,15 +905,34 @@ def small_attention(q, k, v, out, B, Tq, Tk, NH, hd, ldq, ldk, ldv, ldo):
     return out
 
 
+MAX_PROMPT_TOKENS = 256     # tokens per prompt set (5 output tokens + sparse prompts): PSAM_MAX_PROMPT_TOKENS of the C side
+
+
+def token_attention(q, k, v, out, B, Tq, Tk, NH, hd, ldq, ldk, ldv, ldo):
+    """small_attention for up to MAX_PROMPT_TOKENS keys (psam_token_attention: the keys in chunks of 16 through LDS)."""
+    q16 = q.dtype == torch.float16
+    _req(k, torch.float32, "k"); _req(v, torch.float32, "v")
+    assert out.dtype == q.dtype
+    st = _lib.lib().psam_token_attention(_ptr(q), _ptr(k), _ptr(v), _ptr(out), B, Tq, Tk, NH, hd, ldq, ldk, ldv, ldo,
+                                        1 if q16 else 0, _stream())
+    _lib.check(st, "psam_token_attention")
+    return out
+
+
+def prompt_attention(q, k, v, out, B, Tq, Tk, NH, hd, ldq, ldk, ldv, ldo):
+    """attention over the Tk tokens of a prompt set: small_attention up to 16 keys (scores in registers), token_attention above"""
+    return (small_attention if Tk <= 16 else token_attention)(q, k, v, out, B, Tq, Tk, NH, hd, ldq, ldk, ldv, ldo)
+
+
 def t2i_split(B, NH, T, Nk, n_cu=256):
     """into how many key ranges a token-to-image attention launch is split (PSAM_T2I_SPLIT: "auto", or a number to force): the unsplit
-    launch has B * NH workgroups whose waves each walk all keys, 64 dependent round trips"""
+    launch has B * NH * ceil(T / 16) workgroups whose waves each walk all keys, 64 dependent round trips"""
     mode = _os.environ.get("PSAM_T2I_SPLIT", "auto")
-    if T > 16 or Nk < 512 or mode in ("0", "1"):        # (a forced count of 1 is one range: no split)
+    if T > MAX_PROMPT_TOKENS or Nk < 512 or mode in ("0", "1"):        # (a forced count of 1 is one range: no split)
         return 1
     if mode != "auto":
         return max(1, min(16, Nk // 256, int(mode)))
-    return max(1, min(16, Nk // 256, n_cu // (B * NH)))
+    return max(1, min(16, Nk // 256, n_cu // (B * NH * max(1, (T + 15) // 16))))
 
 
 def t2i_attention(q, K, V, out, B, T, Nk, NH, head_major=False, split=None):

@@ -110,8 +110,9 @@ class MaskDecoder(nn.Module):
         g = int(round(Nk ** 0.5))
         if g * g != Nk:
             raise NotImplementedError("a square g x g image embedding")
-        if T > 16:
-            raise NotImplementedError("more than 11 sparse prompt tokens per prompt set")
+        if T > ops.MAX_PROMPT_TOKENS:
+            raise NotImplementedError(f"{T} tokens per prompt set: more than {ops.MAX_PROMPT_TOKENS} "
+                                      f"({ops.MAX_PROMPT_TOKENS - 5} sparse prompt tokens)")
         ws = self._workspace(B, T, Nk, tokens.device)
         lin = ops.small_linear
         h16 = self.image_side_fp16

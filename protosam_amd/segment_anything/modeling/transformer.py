@@ -1,9 +1,9 @@
 """SAM's two-way transformer on the HIP kernels (names of models/segment_anything/modeling/transformer.py:16-240).
 
 `TwoWayTransformer.run_tokens` is the decoder's hot path (MaskDecoder.predict_masks_tokens drives it): B prompt sets against
-the token-major embedding(s) of their image(s), everything in buffers of a per-shape workspace. Token side (T <= 16 tokens
-per prompt set): fp32 `small_linear` / `small_attention`. Image side (4096 tokens): the k / v / q projections and the
-image-to-token out-projection are GEMMs at fp32 accuracy (`psam_gemm_f32x3`, or the exact-fp32 MFMA `psam_gemm_f32`; `keys + pe`
+the token-major embedding(s) of their image(s), everything in buffers of a per-shape workspace. Token side (T tokens per
+prompt set, up to ops.MAX_PROMPT_TOKENS): fp32 `small_linear` and `small_attention` (T <= 16) or `token_attention` (above).
+Image side (4096 tokens): the k / v / q projections and the image-to-token out-projection are GEMMs at fp32 accuracy (`psam_gemm_f32x3`, or the exact-fp32 MFMA `psam_gemm_f32`; `keys + pe`
 is added on the operand load); token-to-image attention is `psam_t2i_attention`.
 
 The modules' own `forward`s (transformer.py:62-106 TwoWayTransformer, :151-182 TwoWayAttentionBlock, :218-240 Attention) are
@@ -58,8 +58,9 @@ class Attention(nn.Module):
     @torch.no_grad()
     def forward(self, q, k, v):
         """transformer.py:218-240: out_proj(softmax(q_proj(q) k_proj(k)^T / sqrt(c)) v_proj(v)); q [B,Nq,C], k / v [B,Nk,C] fp32 ->
-        [B,Nq,C]. Kernels by shape: <= 16 keys `psam_small_attention` (token self-attention, image-to-token), otherwise <= 16
-        queries over <= 4096 keys `psam_t2i_attention` (token-to-image, 16-wide heads)."""
+        [B,Nq,C]. Kernels by shape: <= 16 keys `psam_small_attention`, <= MAX_PROMPT_TOKENS keys with 16- or 32-wide heads
+        `psam_token_attention` (token self-attention, image-to-token), otherwise <= MAX_PROMPT_TOKENS queries over <= 4096 keys
+        `psam_t2i_attention` (token-to-image, 16-wide heads)."""
         ap = self._pack()
         B, Nq, C = q.shape
         Nk = k.shape[1]
@@ -69,13 +70,15 @@ class Attention(nn.Module):
         kp = ops.small_linear(k2, ap["kw"], ap["kb"])
         vp = ops.small_linear(v2, ap["vw"], ap["vb"])
         att = torch.empty_like(qp)
-        if Nk <= 16:
-            ops.small_attention(qp, kp, vp, att, B, Nq, Nk, NH, ci // NH, ci, ci, ci, ci)
-        elif Nq <= 16 and Nk <= 4096 and ci // NH == 16:
+        cap = ops.MAX_PROMPT_TOKENS
+        if Nk <= 16 or (Nk <= cap and ci // NH in (16, 32) and NH <= 8):
+            ops.prompt_attention(qp, kp, vp, att, B, Nq, Nk, NH, ci // NH, ci, ci, ci, ci)
+        elif Nq <= cap and Nk <= 4096 and ci // NH == 16:
             ops.t2i_attention(qp, kp, vp, att, B, Nq, Nk, NH)
         else:
             raise NotImplementedError(f"Attention.forward: {Nq} queries x {Nk} keys with {ci // NH}-wide heads has no HIP kernel "
-                                      "(<= 16 keys, or <= 16 queries over <= 4096 keys with 16-wide heads)")
+                                      f"(<= 16 keys, <= {cap} keys with 16- or 32-wide heads, or <= {cap} queries over <= 4096 keys "
+                                      "with 16-wide heads)")
         return ops.small_linear(att, ap["ow"], ap["ob"]).view(B, Nq, C)
 
 
@@ -85,7 +88,7 @@ class _Run:
     def __init__(self, ws, B, T, Nk, NH, tok_pe, pe_tok, h16, x3):
         self.ws, self.B, self.T, self.Nk, self.NH, self.tok_pe, self.pe_tok, self.h16, self.x3 = ws, B, T, Nk, NH, tok_pe, pe_tok, h16, x3
         # K / V of the token-to-image attention head-major (contiguous 64-byte key rows; the kernels are written for 16-wide heads)
-        self.hm = (not h16) and T <= 16 and Nk >= 64 and 128 // NH == 16
+        self.hm = (not h16) and Nk >= 64 and 128 // NH == 16
         self.t2i_s = ops.t2i_split(B, NH, T, Nk) if NH == 8 else 1     # key ranges per (prompt set, head): few prompt sets leave the CUs idle
 
     def img_proj(self, w_name, ap, out, with_pe, heads=None):
@@ -163,7 +166,7 @@ class TwoWayAttentionBlock(nn.Module):
         lin(src, sa["qw"], sa["qb"], out=ws["tq"], x2=x2)
         lin(src, sa["kw"], sa["kb"], out=ws["tk"], x2=x2)
         lin(src, sa["vw"], sa["vb"], out=ws["tv"])
-        ops.small_attention(ws["tq"], ws["tk"], ws["tv"], ws["ta"], B, T, T, NH, 256 // NH, 256, 256, 256, 256)
+        ops.prompt_attention(ws["tq"], ws["tk"], ws["tv"], ws["ta"], B, T, T, NH, 256 // NH, 256, 256, 256, 256)
         lin(ws["ta"], sa["ow"], sa["ob"], out=ws["t1"], resid=None if L["skip_pe"] else src)
         ops.layernorm(ws["t1"], L["n"][0][0], L["n"][0][1], LN_EPS, out=q, out_dtype=torch.float32)
         r.t2i(L["t2i"], L["n"][1])
@@ -178,8 +181,8 @@ class TwoWayAttentionBlock(nn.Module):
         r.img_proj("qw", ia, ws["p0"], True)
         lin(q, ia["kw"], ia["kb"], out=ws["tk"][:, :128], x2=r.tok_pe)
         lin(q, ia["vw"], ia["vb"], out=ws["tv"][:, :128])
-        ops.small_attention(ws["p0"], ws["tk"][:, :128], ws["tv"][:, :128], ws["p1"], B, Nk, T, NH, 128 // NH, 128,
-                            256, 256, 128)
+        ops.prompt_attention(ws["p0"], ws["tk"][:, :128], ws["tv"][:, :128], ws["p1"], B, Nk, T, NH, 128 // NH, 128,
+                             256, 256, 128)
         if r.h16:
             ops.gemm(ws["p1"], ia["ow16"], ia["ob"], out=keys, epilogue=ops.EPI_F32, resid=keys)
         elif r.x3:
@@ -209,8 +212,9 @@ class TwoWayAttentionBlock(nn.Module):
 def _check_shapes(C, T, Nk, NH):
     if C != 256 or NH != 8:
         raise NotImplementedError("the HIP two-way transformer is built for SAM's 256 channels and 8 heads (build_sam.py:84-90)")
-    if T > 16:
-        raise NotImplementedError("more than 11 sparse prompt tokens per prompt set")
+    if T > ops.MAX_PROMPT_TOKENS:
+        raise NotImplementedError(f"{T} tokens per prompt set: more than {ops.MAX_PROMPT_TOKENS} "
+                                  f"({ops.MAX_PROMPT_TOKENS - 5} sparse prompt tokens)")
     if Nk > 4096:
         raise NotImplementedError("more than 4096 image tokens")
 
