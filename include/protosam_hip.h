@@ -380,6 +380,26 @@ int psam_neg_points(const int* labels, const float* pbg, const double* tab, int 
 int psam_neg_points_batch(const int* labels, const float* pbg, long long pbg_stride, const double* tabs, int cap, int P, int H,
                           int W, int max_comp, int r, float thr, unsigned long long* keys, void* stream);
 
+/* The k most confident pixels of every component (num_points_for_sam = k > 1), models/ProtoSAM.py:266-289 (get_most_conf_points:
+ * torch.topk(output_p_fg[mask], k) per component), with the tie rule of the component table: largest p_fg first, first pixel in
+ * raster order among equals. labels int32 [P,H,W] as psam_ccl_batch writes them (0 = background or a component beyond the table,
+ * component c = label c + 1), pfg fp32 >= 0 with pfg_stride floats between planes, tabs fp64 [P][8 + 12*cap] (read on the device
+ * for tab[1] and tab[3]). keys uint64 [P][R][k], R = max_comp, or R = 1 with only_best (the row of component tab[3], what use_cca
+ * keeps): row c = the k largest keys float_bits(p_fg) << 32 | (0xFFFFFFFF - y*W - x) of component c's pixels in descending order;
+ * a component of fewer than k pixels fills its first `area` slots, the others are 0; rows of components >= min(tab[1], max_comp)
+ * are 0; every element of keys is written. Radix select with per-component byte histograms (integer atomics, pre-aggregated per
+ * wave), compaction, one bitonic sort per row (csrc/topk_points.hip). scratch: 8-byte aligned, psam_topk_points_workspace bytes.
+ * Status 1 before any launch: k < 1 or k > PSAM_MAX_PROMPT_TOKENS - 5, max_comp < 1 or > cap, cap > 4096, P, H or W <= 0,
+ * P > 65535, H*W > 2^31 - 1, a null pointer, scratch too small or misaligned. */
+int psam_topk_points_workspace(int P, int max_comp, int only_best, long long* bytes);
+int psam_topk_points_batch(const int* labels, const float* pfg, long long pfg_stride, const double* tabs, int cap, int P, int H,
+                           int W, int k, int max_comp, int only_best, unsigned long long* keys, void* scratch,
+                           long long scratch_bytes, void* stream);
+/* psam_topk_points_batch for one plane (models/ProtoSAM.py:266-289): labels int32 [H,W], pfg fp32 [H,W], tab fp64 [8 + 12*cap],
+ * keys uint64 [R][k]. */
+int psam_topk_points(const int* labels, const float* pfg, const double* tab, int cap, int H, int W, int k, int max_comp,
+                     int only_best, unsigned long long* keys, void* scratch, long long scratch_bytes, void* stream);
+
 /* Slice hand-off from a scan volume (raw NIfTI voxels [Z,H,W]; vol_dtype 0 int16, 1 float32, 2 uint8, 3 int32).
  * psam_volume_stats: out[0] = sum(x), out[1] = sum(x^2) in fp64, x = voxel*slope + inter  (MR_normalize / get_CT_statistics,
  *   dataloaders/dataset_utils.py:76-108).

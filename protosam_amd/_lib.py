@@ -88,6 +88,9 @@ SIGNATURES = {
                            c_void_p, c_void_p],
     "psam_neg_points": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p],
     "psam_neg_points_batch": [c_void_p, c_void_p, c_longlong, c_void_p] + [c_int] * 6 + [c_float, c_void_p, c_void_p],
+    "psam_topk_points_workspace": [c_int, c_int, c_int, ctypes.POINTER(c_longlong)],
+    "psam_topk_points_batch": [c_void_p, c_void_p, c_longlong, c_void_p] + [c_int] * 7 + [c_void_p, c_void_p, c_longlong, c_void_p],
+    "psam_topk_points": [c_void_p, c_void_p, c_void_p] + [c_int] * 6 + [c_void_p, c_void_p, c_longlong, c_void_p],
     "psam_mask_downscale": [c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p],
     "psam_plane_stats": [c_void_p, c_int, c_int, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p],
     "psam_rle_workspace": [c_int, c_int, ctypes.POINTER(c_longlong)],

@@ -1546,6 +1546,84 @@ def decode_point_key(key, W):
     return idx % W, idx // W, struct.unpack("<f", struct.pack("<I", key >> 32))[0]
 
 
+_topk_scratch = {}
+
+
+def topk_points_workspace(P, max_comp, only_best=False):
+    """Bytes of scratch psam_topk_points(_batch) needs for P planes (psam_topk_points_workspace)."""
+    nbytes = _lib.c_longlong(0)
+    _lib.check(_lib.lib().psam_topk_points_workspace(P, max_comp, 1 if only_best else 0, nbytes), "psam_topk_points_workspace")
+    return nbytes.value
+
+
+def _topk_workspace(P, max_comp, only_best, device):
+    """int64 scratch of topk_points_workspace bytes, one per (device, planes, rows) seen. Calls on one stream share it in order."""
+    key = (str(device), P, max_comp, bool(only_best))
+    if key not in _topk_scratch:
+        _topk_scratch[key] = torch.empty((topk_points_workspace(P, max_comp, only_best) + 7) // 8, dtype=torch.int64, device=device)
+    return _topk_scratch[key]
+
+
+def topk_points_batch(labels, pfg, tabs, k, max_comp, only_best=False, keys=None, scratch=None):
+    """The k most confident pixels of every component of P planes in one launch chain (psam_topk_points_batch): labels int32
+    [P,H*W] or [P,H,W] (psam_ccl_batch's, e.g. ws.labels_b[:P]), p_fg fp32 [P,H,W] view with any plane stride (channel 1 of a
+    [P,2,H,W] probability map), tabs fp64 [P, 8 + 12*cap] -> int64 keys [P, R, k], R = max_comp or 1 with only_best (the component
+    tab[3]): row c = component c's k largest point keys in descending order (largest p_fg first, raster order among equals), zeros
+    behind a component of fewer than k pixels and in the rows of components that do not exist. `scratch`: int64 tensor of
+    topk_points_workspace bytes (default: cached per shape)."""
+    _req(pfg, torch.float32, "pfg")
+    assert labels.dtype == torch.int32 and labels.is_cuda and labels.is_contiguous()
+    assert tabs.dtype == torch.float64 and tabs.is_cuda and tabs.is_contiguous() and tabs.dim() == 2
+    P, H, W = pfg.shape
+    assert pfg.stride(1) == W and labels.numel() == P * H * W and tabs.shape[0] == P
+    assert (tabs.shape[1] - CC_HDR) % CC_STRIDE == 0
+    cap = (tabs.shape[1] - CC_HDR) // CC_STRIDE
+    R = 1 if only_best else max_comp
+    if keys is None:
+        keys = torch.empty((P, R, k), dtype=torch.int64, device=pfg.device)
+    assert keys.dtype == torch.int64 and keys.is_cuda and keys.is_contiguous() and keys.numel() >= P * R * k
+    if scratch is None:
+        scratch = _topk_workspace(P, max_comp, only_best, pfg.device)
+    assert scratch.dtype == torch.int64 and scratch.is_cuda and scratch.is_contiguous()
+    st = _lib.lib().psam_topk_points_batch(_ptr(labels), _ptr(pfg), pfg.stride(0), _ptr(tabs), cap, P, H, W, k, max_comp,
+                                           1 if only_best else 0, _ptr(keys), _ptr(scratch), scratch.numel() * 8, _stream())
+    _lib.check(st, "psam_topk_points_batch")
+    return keys
+
+
+def topk_points(ws, pfg, tab, k, max_comp, only_best=False, keys=None, labels=None, scratch=None):
+    """int64 keys [R, k] (see topk_points_batch) of one plane: ws.labels (the CCL of the SAME image; or `labels`), p_fg fp32
+    [H,W], tab the fp64 table of that labelling (capacity ws.cap)."""
+    _req(pfg, torch.float32, "pfg")
+    assert pfg.is_contiguous() and tab.dtype == torch.float64 and tab.is_cuda and tab.is_contiguous()
+    assert tab.numel() == CC_HDR + CC_STRIDE * ws.cap and pfg.numel() == ws.H * ws.W
+    labels = ws.labels if labels is None else labels
+    assert labels.dtype == torch.int32 and labels.is_cuda and labels.is_contiguous() and labels.numel() == ws.H * ws.W
+    R = 1 if only_best else max_comp
+    if keys is None:
+        keys = torch.empty((R, k), dtype=torch.int64, device=pfg.device)
+    assert keys.dtype == torch.int64 and keys.is_cuda and keys.is_contiguous() and keys.numel() >= R * k
+    if scratch is None:
+        scratch = _topk_workspace(1, max_comp, only_best, pfg.device)
+    assert scratch.dtype == torch.int64 and scratch.is_cuda and scratch.is_contiguous()
+    st = _lib.lib().psam_topk_points(_ptr(labels), _ptr(pfg), _ptr(tab), ws.cap, ws.H, ws.W, k, max_comp, 1 if only_best else 0,
+                                     _ptr(keys), _ptr(scratch), scratch.numel() * 8, _stream())
+    _lib.check(st, "psam_topk_points")
+    return keys
+
+
+def decode_topk_keys(row, W):
+    """One row of topk_points keys (ints, possibly negative from the int64 view) -> [(x, y, p), ...] in the row's order, up to the
+    first 0 (a component of fewer pixels than the row has slots)."""
+    out = []
+    for key in row:
+        pt = decode_point_key(int(key), W)
+        if pt is None:
+            break
+        out.append(pt)
+    return out
+
+
 def volume_stats(vol, vol_dtype, slope=1.0, inter=0.0):
     """fp64 [2] = {sum(x), sum(x^2)} of x = voxel*slope + inter over a raw device volume (psam_volume_stats)."""
     assert vol.is_cuda and vol.is_contiguous()

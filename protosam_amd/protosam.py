@@ -23,8 +23,12 @@ Negative points (`use_neg_points=True`, ProtoSAM.py:361-372,395-419,508-511): `p
 most confident background pixel of each component's 10-pixel dilation ring and the global one (p_bg >= 0.95); components
 whose prompt sets end up with different token counts are decoded in separate batches.
 `degrees_rotate != 0` runs the coarse model on the rotated query and rotates its logits back (protosam_amd/rotate.py).
-`num_points_for_sam` = k > 1: the k most confident pixels of every component (`_topk_points`: the reference's own host-side
-`torch.topk` call on the kernels' probabilities), k = 1 comes from the component table on the device.
+`num_points_for_sam` = k > 1: the k most confident pixels of every component; k = 1 comes from the component table on the device.
+PSAM_TOPK_POINTS = "host" (default): `_topk_points`, the reference's own host-side `torch.topk` call on the kernels' probabilities
+(two 4 MB downloads per plane and a wait after every chunk of planes), which also reproduces torch.topk's order among equal
+probabilities - an artefact of its partial sort that the reference's recorded runs pin. "device": `psam_topk_points_batch`
+right behind the connected components, no download and no wait; the tie rule is the component table's - largest probability
+first, raster order among equals - so the chosen probabilities are the same and tied points may be other pixels.
 Unsupported (outside SURVEY §8's hot path, raise NotImplementedError): `debug` plotting, training mode.
 """
 import os
@@ -54,6 +58,8 @@ MAX_COMPONENTS = 256          # fast path: table rows per slice that travel D2H 
 MAX_COMPONENTS_LARGE = 4096   # psam_ccl's limit; used for a slice that overflows the fast table
 DECODER_CHUNK = 256           # prompt sets per decoder call (workspace ~ 25 MB per prompt set)
 MAX_NEG_COMPONENTS = 64   # psam_neg_points launches one tile grid per component
+MAX_TOPK_COMPONENTS = 64  # key rows per plane of the batched psam_topk_points_batch; a plane with more asks again on its own
+TOPK_MODES = ("host", "device")
 CCL_SLOTS = 32            # planes per connected-components launch chain of the batched paths (~8 MB of scratch per slot at 1024^2)
 
 
@@ -319,6 +325,12 @@ class ProtoSAM(nn.Module):
         # kernels blur those), "1" always, "0" never. Same results. One slice per call (the reference's convention) gains most:
         # 88.0 -> 100.6 slices/s, the coarse model's ~150 small launches run beside the encoder's GEMMs.
         self.overlap_streams = os.environ.get("PSAM_OVERLAP_STREAMS", "auto")
+        # num_points_for_sam > 1: where the k most confident pixels of a component are found (see the module docstring). "host"
+        # stays the default because torch.topk's order among equal probabilities, which the reference's records pin, is not
+        # reproducible on the device.
+        self.topk_points = os.environ.get("PSAM_TOPK_POINTS", "host")
+        if self.topk_points not in TOPK_MODES:
+            raise ValueError(f"PSAM_TOPK_POINTS must be one of {TOPK_MODES}, got {self.topk_points!r}")
         self._dense_run = 0
 
     def get_sam(self, checkpoint_path, use_sam_trans):
@@ -492,6 +504,24 @@ class ProtoSAM(nn.Module):
             out[cid] = torch.nonzero(mask)[idx][:, [1, 0]].numpy().astype(np.float64)
         return out
 
+    def _wants_topk(self):
+        """num_points_for_sam = k > 1 reaches the prompts (confidence points are on)"""
+        return self.num_points_for_sam > 1 and self.use_points and self.point_mode in (CONF_MODE, BOTH_MODE)
+
+    def _topk_from_keys(self, keys, tab, ids, plane=None):
+        """PSAM_TOPK_POINTS=device: int64 numpy keys [R, k] of psam_topk_points (row r = component ids[r] - 1; with use_cca the
+        one row of the kept component) -> {label: float64 [k, 2] (x, y)}, what `_topk_points` returns. A component of fewer
+        than k pixels raises (the host path raises torch.topk's RuntimeError there, as the reference does)."""
+        S, k = self.sam.image_encoder.img_size, self.num_points_for_sam
+        out = {}
+        for cid in ids:
+            pts = ops.decode_topk_keys(keys[0 if self.use_cca else cid - 1], S)
+            if len(pts) < k:
+                area = int(tab[ops.CC_HDR + ops.CC_STRIDE * (cid - 1)])
+                raise RuntimeError(f"plane {plane}: component {cid - 1} has {area} pixels, fewer than num_points_for_sam = {k}")
+            out[cid] = np.array([[x, y] for x, y, _ in pts], dtype=np.float64)
+        return out
+
     def _prompts_from_table(self, tab, neg_keys=None, topk=None):
         """tab: fp64 numpy table of csrc/ccl.hip; neg_keys: int64 numpy keys of psam_neg_points (use_neg_points).
         Returns per kept component a list of (x, y) and a list of labels in the prompt kernel's convention (1 = positive
@@ -558,6 +588,7 @@ class ProtoSAM(nn.Module):
                       tabs_host=torch.empty((P, ops.CC_HDR + ops.CC_STRIDE * MAX_COMPONENTS), dtype=torch.float64).pin_memory(),
                       neg_keys=torch.empty((P, MAX_NEG_COMPONENTS + 1), dtype=torch.int64, device=dev),
                       neg_keys_host=torch.empty((P, MAX_NEG_COMPONENTS + 1), dtype=torch.int64).pin_memory(),
+                      topk_keys=None, topk_keys_host=None,
                       lab256=torch.empty((P, S // 4, S // 4), dtype=torch.int32, device=dev) if self._mask_only else None,
                       fg_event=torch.cuda.Event(), event=torch.cuda.Event(), sam_done=torch.cuda.Event())
         if bb.get("B", 0) < B:
@@ -565,6 +596,10 @@ class ProtoSAM(nn.Module):
             bb.update(q1024=torch.empty((B, 3, S, S), dtype=torch.float32, device=dev),
                       mm=torch.empty(2 * B, dtype=torch.int32, device=dev),
                       patches=torch.empty((B * 4096, 768), dtype=torch.float16, device=dev))
+        shape = (bb["P"], 1 if self.use_cca else MAX_TOPK_COMPONENTS, self.num_points_for_sam)
+        if self.topk_points == "device" and self._wants_topk() and (bb["topk_keys"] is None or bb["topk_keys"].shape != shape):
+            bb.update(topk_keys=torch.empty(shape, dtype=torch.int64, device=dev),
+                      topk_keys_host=torch.empty(shape, dtype=torch.int64).pin_memory())
         slots = min(P, CCL_SLOTS)
         if bb.get("ccl") is None or bb["ccl"].slots < slots:
             bb["ccl"] = None
@@ -713,9 +748,10 @@ class ProtoSAM(nn.Module):
         # connected components in chunks of planes; whatever reads a chunk's labels (host top-k, the ring search beyond the fast
         # key rows) runs before the next chunk overwrites them
         cw, pending = bb["ccl"], feat_tok is not None
-        need_labels = self.use_neg_points or (self.num_points_for_sam > 1 and self.use_points
-                                              and self.point_mode in (CONF_MODE, BOTH_MODE))
+        topk_dev = self._wants_topk() and self.topk_points == "device"
+        need_labels = self.use_neg_points or (self._wants_topk() and not topk_dev)
         tabs_h, keys_h = bb["tabs_host"][:P], bb["neg_keys_host"][:P]
+        tk_h = bb["topk_keys_host"][:P] if topk_dev else None
         sets, keep = {}, None
         for c0 in range(0, P, cw.slots):
             c1 = min(c0 + cw.slots, P)
@@ -724,6 +760,10 @@ class ProtoSAM(nn.Module):
             if self.use_neg_points:
                 ops.neg_points_batch(cw.labels_b[:n], prob[c0:c1, 0], cw.tabs[:n], MAX_NEG_COMPONENTS, keys=bb["neg_keys"][c0:c1])
                 keys_h[c0:c1].copy_(bb["neg_keys"][c0:c1], non_blocking=True)
+            if topk_dev:          # the k most confident pixels per component, found while the labels are still there
+                ops.topk_points_batch(cw.labels_b[:n], prob[c0:c1, 1], cw.tabs[:n], self.num_points_for_sam, MAX_TOPK_COMPONENTS,
+                                      only_best=self.use_cca, keys=bb["topk_keys"][c0:c1])
+                tk_h[c0:c1].copy_(bb["topk_keys"][c0:c1], non_blocking=True)
             if self._mask_only:   # cv2.resize(mask, (256, 256), INTER_NEAREST) samples pixel (4y, 4x): one copy per chunk
                 bb["lab256"][c0:c1].copy_(cw.labels_b[:n].view(n, S, S)[:, ::4, ::4])
             tabs_h[c0:c1].copy_(cw.tabs[:n], non_blocking=True)
@@ -745,7 +785,8 @@ class ProtoSAM(nn.Module):
                 for i in range(n):
                     tab = tabs_h[c0 + i].numpy()
                     if int(tab[0]) <= int(tab[1]) and int(tab[1]) > 0:    # (overflow: relabelled below; empty: no prompt)
-                        sets[c0 + i] = self._plane_prompts(tab, prob[c0 + i], keys_h[c0 + i].numpy(), cw, i)
+                        sets[c0 + i] = self._plane_prompts(tab, prob[c0 + i], keys_h[c0 + i].numpy(), cw, i, plane=c0 + i,
+                                                           topk_keys=tk_h[c0 + i].numpy() if topk_dev else None)
         # host: the prompt sets of the other planes
         bb["event"].synchronize()
         tabs = []
@@ -760,7 +801,12 @@ class ProtoSAM(nn.Module):
                     bb["lab256"][p].copy_(big.labels.view(S, S)[::4, ::4])
             tabs.append(tab)
             if int(tab[1]) > 0 and p not in sets:
-                sets[p] = self._plane_prompts(tab, prob[p], None, big)
+                if topk_dev and big is None and not self.use_cca and int(tab[1]) > MAX_TOPK_COMPONENTS:
+                    # more components than the batched call has key rows, and the chunk's labels may be overwritten by now: label
+                    # this plane again (the same numbering) for the one-plane call on all of its components
+                    big = self._ccl_large(pred[p], prob[p, 1], fg[p:p + 1])[0]
+                sets[p] = self._plane_prompts(tab, prob[p], None, big, plane=p,
+                                              topk_keys=tk_h[p].numpy() if topk_dev and big is None else None)
         feat_row = [-1] * B                                                     # slice -> row of feat_tok
         for i, b in enumerate(keep):
             feat_row[b] = i
@@ -802,11 +848,12 @@ class ProtoSAM(nn.Module):
             stats.update(best=best)
         return out, results, tabs, stats
 
-    def _plane_prompts(self, tab, prob, neg_keys, ws=None, slot=0):
+    def _plane_prompts(self, tab, prob, neg_keys, ws=None, slot=0, plane=None, topk_keys=None):
         """One plane's prompt sets from its component table: prob [2,S,S] its softmax, neg_keys its fast negative-point keys, ws /
-        slot the workspace and table row of the labelling the table belongs to (read by the host top-k and by the ring search of
-        all components). -> (coords or None, labels, table rows) as `_prompts_from_table` (coords None for mask prompts, where
-        labels are component ids)."""
+        slot the workspace and table row of the labelling the table belongs to (read by the host top-k and by the ring search and
+        the device top-k of all components). topk_keys: the plane's rows of psam_topk_points_batch (PSAM_TOPK_POINTS=device; None
+        where they belong to another labelling). -> (coords or None, labels, table rows) as `_prompts_from_table` (coords None
+        for mask prompts, where labels are component ids)."""
         S = self.sam.image_encoder.img_size
         n_found, n = int(tab[0]), int(tab[1])
         # component k of the table carries label k + 1 (csrc/ccl.hip); cca keeps the most confident one
@@ -819,7 +866,14 @@ class ProtoSAM(nn.Module):
             # component, ProtoSAM.py:395-419)
             neg_keys = ops.neg_points(ws, prob[0], ws.tabs[slot], n, labels=ws.labels_b[slot]).cpu().numpy()
         topk = None
-        if self.num_points_for_sam > 1 and self.use_points and self.point_mode in (CONF_MODE, BOTH_MODE):
+        if self._wants_topk() and self.topk_points == "device":
+            if topk_keys is None or (not self.use_cca and n > MAX_TOPK_COMPONENTS):
+                # the batched rows hold the first MAX_TOPK_COMPONENTS components of the fast labelling: ask again for this plane
+                # alone, on the labelling the table in hand belongs to (synchronous, rare)
+                topk_keys = ops.topk_points(ws, prob[1], ws.tabs[slot], self.num_points_for_sam, n, only_best=self.use_cca,
+                                            labels=ws.labels_b[slot]).cpu().numpy()
+            topk = self._topk_from_keys(topk_keys, tab, ids, plane)
+        elif self._wants_topk():
             topk = self._topk_points(prob[1], ws.labels_b[slot], S, ids, self.num_points_for_sam)
         return self._prompts_from_table(tab, neg_keys, topk)
 
