@@ -414,6 +414,17 @@ def layernorm(x, weight, bias, eps, out=None, out_dtype=torch.float16, out2=None
     if out is None:
         out = torch.empty((M + zero_tail_rows, D), dtype=out_dtype, device=x.device)
     o2 = out.reshape(-1, out.shape[-1]) if out.dim() != 2 else out
+    if out2 is not None:
+        # the kernel writes out2 only next to an fp16 `out`, as fp32, and indexes it with the row stride of `out`
+        if out.dtype != torch.float16:
+            raise ValueError("out2: the second copy is written only next to an fp16 out (an fp32 out is that copy already)")
+        if out2.dtype != torch.float32:
+            raise ValueError(f"out2: expected torch.float32, got {out2.dtype}")
+        _req(out2, torch.float32, "out2")
+        y2 = out2.reshape(-1, out2.shape[-1]) if out2.dim() != 2 else out2
+        if y2.shape[0] < M or y2.shape[1] < D or (y2.stride(0) != o2.stride(0) and M > 1):
+            raise ValueError(f"out2: needs at least {M} rows of {D} columns with the row stride of out ({o2.stride(0)}), got "
+                             f"{tuple(y2.shape)} with row stride {y2.stride(0)}")
     h = _tstart("layernorm")
     st = _lib.lib().psam_layernorm(_ptr(x2), _ptr(weight), _ptr(bias), _ptr(o2), _ptr(out2), M, D, x2.stride(0),
                                   o2.stride(0), float(eps), 0 if out.dtype == torch.float16 else 1,
