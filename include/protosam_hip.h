@@ -126,6 +126,26 @@ int psam_attention_f16(const void* qkv, void* out, const float* rel_h, const flo
  * (csrc/gattn_asm_gen.py) where it applies - rel-pos: hd = 80 or 64, N a multiple of 256; no bias: hd = 64, N >= 128; any head count
  * and batch - and the DMA-fed HIP kernel elsewhere. */
 int psam_attention_set_variant(int v);
+/* *id = the kernel the most recent psam_attention_f16 / psam_relpos call of this process launched, after every fallback (0 before
+ * the first call): what tests and A/B tools check a label or a forced variant against. The low byte names the kernel family; the
+ * bits above it the template choice that changes the code that ran. Written at the point of launch: a call refused for its arguments leaves the value as it was. */
+#define PSAM_ATTN_KERNEL_ATTN 1        /* attn_kernel (register-staged; windows and both global modes) */
+#define PSAM_ATTN_KERNEL_WATTN 2       /* wattn_kernel */
+#define PSAM_ATTN_KERNEL_WATTN_P 3     /* wattn_p_kernel (persistent) */
+#define PSAM_ATTN_KERNEL_GATTN 4       /* gattn_kernel (DMA-fed) */
+#define PSAM_ATTN_KERNEL_GATTN_ANY 5   /* gattn_any_kernel */
+#define PSAM_ATTN_KERNEL_ASM_REL 6     /* psam_gattn_asm_{80,64}_rel */
+#define PSAM_ATTN_KERNEL_ASM_FUSED 7   /* psam_gattn_asm_{80,64}_fused */
+#define PSAM_ATTN_KERNEL_ASM_NOREL 8   /* psam_gattn_asm_64_norel */
+#define PSAM_ATTN_KERNEL_ASM_WINDOW 9  /* psam_wattn_asm_80 */
+#define PSAM_ATTN_KERNEL_RELPOS 10     /* relpos_mfma_kernel (psam_relpos) */
+#define PSAM_ATTN_KERNEL_FAMILY 0xff   /* mask of the family */
+#define PSAM_ATTN_KERNEL_FULL 0x100    /* the `full` instance (N a multiple of 64) of attn_kernel / gattn_kernel / gattn_any_kernel in
+                                        * modes 0 / 1; clear: the ragged instance, or a kernel that has one form */
+#define PSAM_ATTN_KERNEL_STAGE64 0x200 /* gattn_any_kernel with stage rows of 64 floats (a map side above 32); clear: 32 */
+#define PSAM_ATTN_KERNEL_QT4 0x400     /* relpos_mfma_kernel with four query tiles per wave (N a multiple of 256); clear: one */
+#define PSAM_ATTN_KERNEL_V2 0x800      /* attn_kernel in modes 0 / 1 with the V2 softmax; clear: the serial form */
+int psam_attention_last_kernel(int* id);
 /* 1 when psam_attention_f16(mode 1) computes the rel-pos terms itself from `rpack` for this shape (64 x 64 token map, hd 80 / 64,
  * token-major qkv, the assembly kernels selected), else 0: the caller then runs psam_relpos first.
  * image_encoder.py:325-372 (add_decomposed_rel_pos) inside :235-251. Returns 0 / 1, not a status. */

@@ -25,8 +25,11 @@ U16 = 2.0 ** -11            # unit roundoff of fp16
 TINY16 = 2.0 ** -24         # smallest fp16 subnormal: what a P that underflows can lose per key
 RMS_FACTOR = 3.0
 
+# what a wrong map from workgroup id to (image, head, window or query block) does: the arithmetic of every item is right, its place
+# is not. An item is one (image, head, window) in mode 2 and one (image, head, block of `item_rows` queries) in modes 0 / 1.
+ITEM_FAULTS = ("drop_item", "swap_heads", "wrong_image", "repeat_item_skip_next")
 FAULTS = ("drop_key", "phantom_tail", "swap_keys", "relh_transposed", "rel_row_off_by_one", "rel_scaled_q", "pad_key_zero",
-          "unpartition_shift")
+          "unpartition_shift") + ITEM_FAULTS
 
 
 # ---- geometry ----------------------------------------------------------------------------------------------------------------
@@ -74,9 +77,66 @@ def _rel_index(n, rh, rw, device, fault):
     return ih, iw
 
 
+def item_slots(mode, N, gh=0, gw=0, item_rows=256, ws=WS, device="cpu"):
+    """[items per (image, head), slots] int64: the token of every query slot of every item, -1 where the slot holds no token (beyond
+    the map in a window, beyond N in the last query block)."""
+    if mode == 2:
+        return window_tokens(gh, gw, ws).to(device)
+    nqb = -(-N // item_rows)
+    t = torch.arange(nqb * item_rows, device=device).view(nqb, item_rows)
+    return torch.where(t < N, t, torch.full_like(t, -1))
+
+
+def item_fault(o, fault, arg, slots, mode, H, hd, guard):
+    """o [B, N, H * hd] of the sound arithmetic -> [B + guard, N, H * hd] as a kernel with a broken item map would leave a NaN-filled
+    buffer with `guard` images of guard rows behind it.
+      drop_item              arg (b, h, r): item r of (b, h) is never run - its rows keep the prefill
+      swap_heads             arg (b, h, h2): the results of heads h and h2 of image b exchanged
+      wrong_image            arg (b, h, b2): every item of (b, h) computed from image b2's q / k / v
+      repeat_item_skip_next  arg (b, h, r): the result of item i = (b, h, r) is also written to the place of item i + 1, which is never
+                             run; i + 1 in the order the kernels walk: the next head of the window, then the next window, then the
+                             next image (mode 2) / the next query block of the head, then the next head, then the next image"""
+    B, N, C = o.shape
+    buf = torch.full((B + guard, N, C), float("nan"), dtype=o.dtype, device=o.device)
+    buf[:B] = o
+
+    def cols(h):
+        return slice(h * hd, (h + 1) * hd)
+
+    if fault == "drop_item":
+        b, h, r = arg
+        t = slots[r]
+        buf[b, t[t >= 0], cols(h)] = float("nan")
+    elif fault == "swap_heads":
+        b, h, h2 = arg
+        assert h != h2
+        buf[b, :, cols(h)], buf[b, :, cols(h2)] = o[b, :, cols(h2)], o[b, :, cols(h)]
+    elif fault == "wrong_image":
+        b, h, b2 = arg
+        assert b != b2
+        buf[b, :, cols(h)] = o[b2, :, cols(h)]
+    else:
+        b, h, r = arg
+        R = slots.shape[0]
+        if mode == 2:
+            h2 = (h + 1) % H
+            r2 = r + (h2 == 0)
+            b2, r2 = b + (r2 == R), r2 % R
+        else:
+            r2 = (r + 1) % R
+            h2 = h + (r2 == 0)
+            b2, h2 = b + (h2 == H), h2 % H
+        assert b2 < B + guard, "the repeated write falls behind the buffer: give the fault guard rows to land in"
+        src, dst = slots[r], slots[r2]
+        val = torch.full((slots.shape[1], hd), float("nan"), dtype=o.dtype, device=o.device)
+        val[src >= 0] = o[b, src[src >= 0], cols(h)]
+        buf[b2, dst[dst >= 0], cols(h2)] = val[dst >= 0]
+    return buf
+
+
 # ---- the arithmetic ----------------------------------------------------------------------------------------------------------
 def reference(qkv, mode, scale=None, Rh=None, Rw=None, pad_row=None, gh=0, gw=0, ws=WS, budget=True, model=False, targets=None,
-              fault=None, fault_arg=None):
+              fault=None, fault_arg=None, item_rows=256, guard=0):
     """qkv fp16 [B, N, 3, H, hd] (token-major), Rh / Rw fp32 [2 rh - 1, hd] tables (modes 1 / 2), pad_row fp16 [3, H, hd] (mode 2).
 
     Returns a namespace of float64 tensors:
@@ -89,7 +149,8 @@ def reference(qkv, mode, scale=None, Rh=None, Rw=None, pad_row=None, gh=0, gw=0,
       margin [B, H, N]       score of the target key minus the largest score of a key that carries another (k, v) row
                              (targets = int64 [B, H, G, n], a key slot per query slot of every region; padded keys of a window
                              all carry pad_row and count as one)
-    `fault` (tests only) breaks the float64 arithmetic the way a kernel could: see FAULTS."""
+    `fault` (tests only) breaks the float64 arithmetic the way a kernel could: see FAULTS. An ITEM_FAULTS fault leaves the arithmetic
+    alone and misplaces whole items (`item_fault`): `o` is then [B + guard, N, H * hd], NaN where nothing was written."""
     assert fault is None or fault in FAULTS
     B, N, three, H, hd = qkv.shape
     assert three == 3 and qkv.dtype == torch.float16
@@ -169,6 +230,8 @@ def reference(qkv, mode, scale=None, Rh=None, Rw=None, pad_row=None, gh=0, gw=0,
                 other = s.masked_fill(same, -math.inf).max(-1).values
                 out.margin[b, h][tok[real]] = (st - other)[real]
             del s, e
+    if fault in ITEM_FAULTS:
+        out.o = item_fault(out.o, fault, fault_arg, item_slots(mode, N, gh, gw, item_rows, ws, dev), mode, H, hd, guard)
     return out
 
 
@@ -341,7 +404,8 @@ def diffuse(mode, B, H, hd, N=0, gh=0, gw=0, std=0.5, seed=0, device="cpu", spik
 
 def constant_v(mode, B, H, hd, N=0, gh=0, gw=0, seed=0, device="cpu", spiky=False):
     """Every v row, pad_row's included, is one fp16 vector c per head with |c_d| in [0.5, 2) and mixed signs; q, k at 0.5 * randn,
-    once diffuse and once with the spike pattern. Any correct softmax returns c."""
+    once diffuse and once with the spike pattern. Any correct softmax returns c. (c differs between heads, not between images: a
+    result on the wrong head fails here, one from the wrong image only on the selectors.)"""
     case = diffuse(mode, B, H, hd, N, gh, gw, 0.5, seed, "cpu", spiky)
     g = _gen(seed + 7919)
     mag = 0.5 + 1.49 * torch.rand((H, hd), generator=g)
@@ -455,6 +519,19 @@ def check_budget(out, case, ref):
     return float(ratio.max()), float(r.max())
 
 
+def check_guard(buf, B):
+    """buf fp16 [B + guard, N, C], NaN before the launch: the images behind the B real ones must still be NaN everywhere. Returns the
+    number of guard elements."""
+    tail = buf[B:]
+    assert tail.numel() > 0, "no guard rows"
+    bad = ~torch.isnan(tail.float())
+    if bool(bad.any()):
+        i, r, col = bad.nonzero()[0].tolist()
+        raise AssertionError(f"guard row {r} behind the last image (guard image {i}), column {col} was written: "
+                             f"{float(tail[i, r, col])}; {int(bad.sum())} guard elements written")
+    return tail.numel()
+
+
 def check_margin(case, ref):
     """The selector's condition, asserted on the float64 reference before a kernel output is looked at. Returns the least margin."""
     m = float(ref.margin.min())
@@ -480,3 +557,32 @@ def shapes():
         s |= {(1, gh * gw, gh, gw, hd) for gh, gw in ANY_MAPS}
         s |= {(2, g * g, g, g, hd) for g in WINDOW_MAPS}
     return sorted(s)
+
+
+# ---- the (image, head) sweeps of tests/test_attention_items_gpu.py: the item maps of the kernels, not their arithmetic ---------------
+ITEMS_WINDOW64_BH = ((1, 1), (1, 3), (1, 5), (3, 5), (2, 7), (1, 12), (3, 12), (2, 16), (1, 32), (3, 32), (11, 1))   # 64 x 64 map, hd = 80
+ITEMS_WINDOW_SMALL = (tuple((g, hd, B, H) for g in (32, 20) for hd in HEAD_DIMS for B, H in ((1, 12), (7, 16), (5, 3)))
+                      + tuple((14, hd, B, H) for hd in HEAD_DIMS for B, H in ((1, 1), (1, 2), (3, 1))))
+ITEMS_ASM_BH = ((1, 1), (1, 7), (1, 12), (5, 12), (2, 16), (3, 33))
+# the last (B, H) the work table of the global assembly kernels admits for H = 48 and 64, each followed by the first it refuses
+ITEMS_ASM_EDGES = ((28, 48), (29, 48), (15, 64), (16, 64))
+ITEMS_FUSED_BH = ((1, 5), (1, 12), (2, 16))
+ITEMS_HIP_BH = ((1, 1), (1, 7), (5, 12), (2, 16))
+ITEMS_ANY_MAPS = ((5, 7), (20, 28))
+
+
+def gattn_asm_admits(B, H):
+    """the work table of the global assembly kernels packs b * H + h and divides it by H with ceil(2^16 / H): csrc/attention.hip
+    gattn_asm_eligible admits B * H < 65536 // H (and H <= 64)."""
+    return 1 <= H <= 64 and B * H < 65536 // H
+
+
+def item_shapes_cpu():
+    """(mode, B, H, hd, N, gh, gw, item_rows) of the sweeps that the CPU can afford: tests/test_attention_reference_cpu.py injects
+    the item faults at each. item_rows: 256 queries per item in the assembly kernels, 128 in the HIP global kernels."""
+    return [(0, 5, 12, 64, 128, 0, 0, 256), (0, 28, 48, 64, 128, 0, 0, 256), (0, 1, 7, 64, 449, 0, 0, 256),
+            (0, 5, 12, 80, 200, 0, 0, 128), (0, 2, 16, 64, 200, 0, 0, 128),
+            (1, 5, 12, 64, 256, 4, 64, 256), (1, 2, 48, 80, 256, 4, 64, 256), (1, 5, 12, 80, 35, 5, 7, 128),
+            (1, 2, 16, 64, 560, 20, 28, 128),
+            (2, 5, 3, 64, 400, 20, 20, 0), (2, 1, 12, 80, 1024, 32, 32, 0), (2, 3, 1, 64, 196, 14, 14, 0),
+            (2, 1, 5, 80, 4096, 64, 64, 0), (2, 2, 12, 80, 4096, 64, 64, 0)]

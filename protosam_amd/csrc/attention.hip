@@ -1914,6 +1914,18 @@ __global__ __launch_bounds__(256, (RL == 32 ? 2 : 1)) void gattn_any_kernel(Attn
   }
 }
 
+// The kernel the most recent launch of this file went to, after every fallback: include/protosam_hip.h PSAM_ATTN_KERNEL_* carries
+// the same numbers (tests/test_cabi_cpu.py compares the two). One host-side store per call, next to the launch.
+enum {
+  AK_ATTN = 1, AK_WATTN = 2, AK_WATTN_P = 3, AK_GATTN = 4, AK_GATTN_ANY = 5, AK_ASM_REL = 6, AK_ASM_FUSED = 7, AK_ASM_NOREL = 8,
+  AK_ASM_WINDOW = 9, AK_RELPOS = 10, AK_FULL = 0x100, AK_STAGE64 = 0x200, AK_QT4 = 0x400, AK_V2 = 0x800
+};
+static int g_last_kernel = 0;
+extern "C" int psam_attention_last_kernel(int* id) {
+  if (!id) return PSAM_ERR_ARG;
+  *id = g_last_kernel;
+  return PSAM_OK;
+}
 static int g_attn_v2 = -1;
 static int g_gattn_any = 0;   // 1: gattn_any_kernel also at gw == 64 when only the packed tables are given (tests, A/B)
 static int g_gattn = -1;   // 1: gattn_kernel for modes 0 / 1
@@ -2003,6 +2015,7 @@ static int launch_gattn_asm(const AttnArgs& p, hipStream_t s, int hd, int kind) 
   size_t sz = sizeof(a);
   void* extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
   const int grid = tab->grid;
+  g_last_kernel = kind == 2 ? AK_ASM_NOREL : kind == 1 ? AK_ASM_FUSED : AK_ASM_REL;
   if (hipModuleLaunchKernel(f, grid, 1, 1, 256, 1, 1, 0, s, nullptr, extra) != hipSuccess) {
     (void)hipGetLastError();
     return PSAM_ERR_LAUNCH;
@@ -2111,6 +2124,7 @@ static int launch_wattn_asm(const AttnArgs& p, hipStream_t s) {
   a.sl2 = p.scale * 1.4426950408889634f; a.isc = 1.0f / p.scale; a.pad0 = a.pad1 = a.pad2 = 0;
   size_t sz = sizeof(a);
   void* extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
+  g_last_kernel = AK_ASM_WINDOW;
   if (hipModuleLaunchKernel(f, grid, 1, 1, 14 * 64, 1, 1, 0, s, nullptr, extra) != hipSuccess) {
     (void)hipGetLastError();
     return PSAM_ERR_LAUNCH;
@@ -2131,14 +2145,17 @@ static int launch_attn(AttnArgs p, int mode, hipStream_t s) {
       int cus, xcds;
       psam_device_geometry(&cus, &xcds);
       const int nitems = p.B * p.nwin * p.H;
+      g_last_kernel = AK_WATTN_P;
       hipLaunchKernelGGL((wattn_p_kernel<HD>), dim3(nitems < cus ? nitems : cus), dim3(14 * 64), 0, s, p, nitems);
       return psam_launch_status();
     }
     if (g_wattn == 1 && p.rpack != nullptr) {
+      g_last_kernel = AK_WATTN;
       hipLaunchKernelGGL((wattn_kernel<HD>), dim3(groups8 * 8 * p.H), dim3(NW * 64), 0, s, p);
       return psam_launch_status();
     }
     // the window kernel sits at its 128-VGPR budget (two workgroups per CU): V2's extra live state spills there, so it keeps V1
+    g_last_kernel = AK_ATTN;
     hipLaunchKernelGGL((attn_kernel<HD, 2, NW, false, false>), dim3(groups8 * 8 * p.H), dim3(NW * 64), 0, s, p);
   } else {
     constexpr int NW = 4;
@@ -2151,6 +2168,7 @@ static int launch_attn(AttnArgs p, int mode, hipStream_t s) {
       // any gh x gw map up to 64 x 64 from the packed tables alone (the host entry checked the sizes): gattn_any_kernel
       if (p.gh > KT || p.gw > KT) return PSAM_ERR_ARG;
       const bool small = p.gh <= 32 && p.gw <= 32;     // stage rows of 32 floats: 74 KB of LDS, two workgroups per CU
+      g_last_kernel = AK_GATTN_ANY | (full ? AK_FULL : 0) | (small ? 0 : AK_STAGE64);
       if (small) {
         if (full) hipLaunchKernelGGL((gattn_any_kernel<HD, 32, true>), grid, block, 0, s, p);
         else hipLaunchKernelGGL((gattn_any_kernel<HD, 32, false>), grid, block, 0, s, p);
@@ -2167,6 +2185,7 @@ static int launch_attn(AttnArgs p, int mode, hipStream_t s) {
     if (g_gattn == 3 && mode == 1 && gattn_asm_eligible(p, mode, HD, 0)) return launch_gattn_asm(p, s, HD, 0);
     if (g_gattn == 3 && mode == 0 && gattn_asm_eligible(p, mode, HD, 2)) return launch_gattn_asm(p, s, HD, 2);
     if (g_gattn && V2) {
+      g_last_kernel = AK_GATTN | (full ? AK_FULL : 0);
       if (mode == 1) {
         if (full) hipLaunchKernelGGL((gattn_kernel<HD, 1, true>), grid, block, 0, s, p);
         else hipLaunchKernelGGL((gattn_kernel<HD, 1, false>), grid, block, 0, s, p);
@@ -2176,6 +2195,7 @@ static int launch_attn(AttnArgs p, int mode, hipStream_t s) {
       }
       return psam_launch_status();
     }
+    g_last_kernel = AK_ATTN | (full ? AK_FULL : 0) | (V2 ? AK_V2 : 0);
     if (mode == 1) {
       if (full) hipLaunchKernelGGL((attn_kernel<HD, 1, NW, true, V2>), grid, block, 0, s, p);
       else hipLaunchKernelGGL((attn_kernel<HD, 1, NW, false, V2>), grid, block, 0, s, p);
@@ -2370,6 +2390,8 @@ extern "C" int psam_relpos(const void* qkv, const void* Rpack, float* rel_h, flo
 #define PSAM_RELPOS_LAUNCH(HD_, QT_)                                                                                        \
   hipLaunchKernelGGL((relpos_mfma_kernel<HD_, QT_>), grid, block, 0, s, (const half_t*)qkv, (const half_t*)Rpack, rel_h, rel_w, \
                      (half_t*)relq, N, H, gw, K, RP, windowed, inv, ts, hs)
+  if (hd != 64 && hd != 80) return PSAM_ERR_ARG;
+  g_last_kernel = AK_RELPOS | (q4 ? AK_QT4 : 0);
   if (hd == 64) { if (q4) PSAM_RELPOS_LAUNCH(64, 4); else PSAM_RELPOS_LAUNCH(64, 1); }
   else if (hd == 80) { if (q4) PSAM_RELPOS_LAUNCH(80, 4); else PSAM_RELPOS_LAUNCH(80, 1); }
   else return PSAM_ERR_ARG;

@@ -482,6 +482,33 @@ def attention_set_variant(v):
     _lib.check(_lib.lib().psam_attention_set_variant(int(v)), "psam_attention_set_variant")
 
 
+# what attention_last_kernel() reports (include/protosam_hip.h PSAM_ATTN_KERNEL_*): the family in the low byte, flags above it
+ATTN_KERNEL_ATTN, ATTN_KERNEL_WATTN, ATTN_KERNEL_WATTN_P, ATTN_KERNEL_GATTN, ATTN_KERNEL_GATTN_ANY = 1, 2, 3, 4, 5
+ATTN_KERNEL_ASM_REL, ATTN_KERNEL_ASM_FUSED, ATTN_KERNEL_ASM_NOREL, ATTN_KERNEL_ASM_WINDOW, ATTN_KERNEL_RELPOS = 6, 7, 8, 9, 10
+ATTN_KERNEL_FAMILY = 0xff
+ATTN_KERNEL_FULL, ATTN_KERNEL_STAGE64, ATTN_KERNEL_QT4, ATTN_KERNEL_V2 = 0x100, 0x200, 0x400, 0x800
+ATTN_KERNEL_NAMES = {1: "attn_kernel", 2: "wattn_kernel", 3: "wattn_p_kernel", 4: "gattn_kernel", 5: "gattn_any_kernel",
+                     6: "psam_gattn_asm_rel", 7: "psam_gattn_asm_fused", 8: "psam_gattn_asm_64_norel", 9: "psam_wattn_asm_80",
+                     10: "relpos_mfma_kernel"}
+
+
+def attention_last_kernel():
+    """The kernel the most recent attention() / relpos() call launched, after every fallback (0 before the first call): an
+    ATTN_KERNEL_* family, or-ed with FULL (the full-tile instance of the HIP global kernels), STAGE64 (gattn_any_kernel's 64-float
+    stage), QT4 (relpos with four query tiles per wave), V2 (attn_kernel's V2 softmax)."""
+    import ctypes
+    k = ctypes.c_int(0)
+    _lib.check(_lib.lib().psam_attention_last_kernel(ctypes.byref(k)), "psam_attention_last_kernel")
+    return k.value
+
+
+def attention_kernel_name(kid):
+    """"gattn_any_kernel+full+stage64" for an id of attention_last_kernel(): what tests print and compare in their messages."""
+    flags = [n for bit, n in ((ATTN_KERNEL_FULL, "full"), (ATTN_KERNEL_STAGE64, "stage64"), (ATTN_KERNEL_QT4, "qt4"),
+                              (ATTN_KERNEL_V2, "v2")) if kid & bit]
+    return "+".join([ATTN_KERNEL_NAMES.get(kid & ATTN_KERNEL_FAMILY, f"kernel {kid & ATTN_KERNEL_FAMILY}")] + flags)
+
+
 def pack_rel_tables(rel_pos_h, rel_pos_w, windowed, hd):
     """fp32 (2K-1, hd) tables -> fp16 [2 (h,w)][2 (hi,lo)][RP][HDP] for psam_relpos (one-time weight packing)."""
     RP = 32 if windowed else 128

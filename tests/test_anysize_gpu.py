@@ -118,20 +118,27 @@ def test_nothing_moves_at_64(dev, H, hd, B):
     scale = hd ** -0.5
     rp = ops.pack_rel_tables(Rh, Rw, False, hd)
     rel_h, rel_w = ops.relpos(qkv, rp, B, N, H, hd, g, g, False, scale)
+    assert ops.attention_last_kernel() == ops.ATTN_KERNEL_RELPOS | ops.ATTN_KERNEL_QT4
     kw = dict(mode=1, rel_h=rel_h, rel_w=rel_w, gh=g, gw=g)
     default = ops.attention(qkv, B, N, H, hd, scale, **kw).float()
+    assert ops.attention_last_kernel() == ops.ATTN_KERNEL_ASM_REL                    # the default dispatch: the assembly kernel
     outs = {}
+    lands = {9: ops.ATTN_KERNEL_ATTN | ops.ATTN_KERNEL_FULL | ops.ATTN_KERNEL_V2, 17: ops.ATTN_KERNEL_GATTN | ops.ATTN_KERNEL_FULL}
     for v in (9, 17):
         ops.attention_set_variant(v)
         try:
             outs[v] = ops.attention(qkv, B, N, H, hd, scale, **kw).float()
+            got = ops.attention_last_kernel()
         finally:
             ops.attention_set_variant(5)
+        assert got == lands[v], (v, ops.attention_kernel_name(got))
     ops.attention_set_variant(5 | 32)
     try:
         anyk = ops.attention(qkv, B, N, H, hd, scale, mode=1, rpack=rp, gh=g, gw=g).float()
+        got = ops.attention_last_kernel()
     finally:
         ops.attention_set_variant(5)
+    assert got == ops.ATTN_KERNEL_GATTN_ANY | ops.ATTN_KERNEL_FULL | ops.ATTN_KERNEL_STAGE64, ops.attention_kernel_name(got)
     ref = _ref_relpos_attention(qkv, Rh, Rw, g, g, scale)
     print(f"H{H} hd{hd} B{B} at 64 x 64: default vs variants 9 / 17 "
           + " / ".join(f"{(default - outs[v]).abs().max().item():.2e}" for v in (9, 17))
@@ -142,6 +149,7 @@ def test_nothing_moves_at_64(dev, H, hd, B):
         torch.testing.assert_close(anyk, outs[v], rtol=2e-3, atol=2e-3)
     torch.testing.assert_close(anyk.double(), ref, rtol=2e-3, atol=2e-3)
     assert torch.equal(ops.attention(qkv, B, N, H, hd, scale, **kw).float(), default)    # bit 5 cleared: the default dispatch again
+    assert ops.attention_last_kernel() == ops.ATTN_KERNEL_ASM_REL
 
 
 def test_larger_maps_stay_an_argument_error(dev):

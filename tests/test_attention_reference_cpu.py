@@ -6,7 +6,11 @@ tests/test_attention_exact_gpu.py holds the attention kernels to.
   * at every shape the GPU file uses: the selector margins (>= 32 nats), and the rounding model passing all three checks;
   * faults injected into the float64 arithmetic - a dropped key, the tail tile's phantom keys, swapped weights, a transposed or
     shifted rel-pos gather, rel-pos terms from the scaled q, a pad key read as zeros, a shifted un-partition - each failing its
-    check at every shape. Nothing here touches a GPU; the faults never reach a kernel.
+    check at every shape. Nothing here touches a GPU; the faults never reach a kernel;
+  * at the (image, head) counts of tests/test_attention_items_gpu.py (`A.item_shapes_cpu()`, H = 12 and H = 48 among them): the
+    constructors' conditions again, and the faults of a wrong ITEM map - an item never run, two heads exchanged, an item computed from
+    another image, an item written twice while its successor is skipped - each refused by at least one of the four things that
+    file checks: the selectors, constant V, the NaN prefill (what `_finite` inside both checks reports) and the guard rows.
 """
 import functools
 
@@ -204,3 +208,107 @@ def test_faults_the_old_tolerance_passes(N, hd, std):
         assert inside > 0.98 and rms > 35 * mdl
         with pytest.raises(AssertionError):
             A.check_budget(bad, case, ref)
+
+
+# ---- item maps: the sweeps of tests/test_attention_items_gpu.py -----------------------------------------------------------------
+ITEM_SHAPES = A.item_shapes_cpu()
+ITEM_IDS = [f"mode{m}-B{B}-H{H}-hd{hd}-N{N}-{gh}x{gw}" for m, B, H, hd, N, gh, gw, _ in ITEM_SHAPES]
+
+
+@functools.lru_cache(maxsize=None)
+def _item_bundle(shape):
+    """the selector and constant-V inputs of the item sweep at the sweep's own (B, H), each with its float64 reference and model."""
+    mode, B, H, hd, N, gh, gw, _ = shape
+    geo = dict(N=N, gh=gh, gw=gw)
+    b = {"qk": A.selector_qk(mode, B, H, hd, seed=31, **geo)}
+    if mode:
+        b["rel"] = A.selector_relpos(mode, B, H, hd, gh, gw, seed=32)
+    b["const"] = A.constant_v(mode, B, H, hd, seed=33, **geo)
+    for name, case in b.items():
+        case.ref = A.reference(case.qkv, mode, budget=False, model=True, targets=case.targets, **A.ref_kwargs(case))
+    return b
+
+
+@pytest.mark.parametrize("shape", ITEM_SHAPES, ids=ITEM_IDS)
+def test_item_sweep_constructors_meet_their_conditions_and_the_model_passes(shape):
+    b = _item_bundle(shape)
+    line = []
+    for name in ("qk", "rel"):
+        if name in b:
+            margin = A.check_margin(b[name], b[name].ref)
+            assert A.check_selector(b[name].ref.model.half(), b[name]) == 0
+            line.append(f"{name} margin {margin:.1f} nats")
+    line.append(f"const model / bound {A.check_constant_v(b['const'].ref.model.half(), b['const']):.3f}")
+    c = b["const"].c
+    assert c.shape[0] == 1 or len({tuple(r.tolist()) for r in c}) == c.shape[0]       # one c per head, no two alike
+    print(f"{ITEM_IDS[ITEM_SHAPES.index(shape)]}: " + ", ".join(line))
+
+
+def _refusals(buf, case, check, B):
+    """which of the item tests' checks refuse this buffer: the family's own check (a NaN it meets is the prefill) and the guard."""
+    seen = []
+    try:
+        check(buf[:B].contiguous(), case)
+    except AssertionError as e:
+        seen.append("NaN prefill" if "not finite" in str(e) else check.__name__)
+    try:
+        A.check_guard(buf, B)
+    except AssertionError:
+        seen.append("guard rows")
+    return seen
+
+
+@pytest.mark.parametrize("shape", ITEM_SHAPES, ids=ITEM_IDS)
+def test_every_item_fault_is_refused(shape):
+    """Each item fault at the first, a middle and the last item: the selector refuses every one of them (by the NaN it meets for
+    a dropped item, by the guard rows too for the repeat of the very last item); constant V, whose c differs between heads only,
+    refuses what moves a result to another head or leaves the prefill, and is blind to `wrong_image` and to a repeat inside one
+    head - recorded below per fault, asserted for the selector."""
+    mode, B, H, hd, N, gh, gw, rows = shape
+    b = _item_bundle(shape)
+    slots = A.item_slots(mode, N, gh, gw, rows or 256)
+    R = slots.shape[0]
+    sid = ITEM_IDS[ITEM_SHAPES.index(shape)]
+    places = sorted({(0, 0, 0), (B // 2, H // 2, R // 2), (B - 1, H - 1, R - 1), (0, H - 1, R - 1)})
+    faults = [("drop_item", p) for p in places] + [("repeat_item_skip_next", p) for p in places]
+    if H > 1:
+        faults += [("swap_heads", (B - 1, 0, H - 1)), ("swap_heads", (0, H // 2, H // 2 - 1))]
+    if B > 1:
+        faults += [("wrong_image", (0, H - 1, B - 1)), ("wrong_image", (B - 1, 0, B - 2))]
+    lines = []
+    for fault, arg in faults:
+        seen = {}
+        for name, check in (("qk", A.check_selector), ("rel", A.check_selector), ("const", A.check_constant_v)):
+            if name not in b:
+                continue
+            case = b[name]
+            clean = case.ref.model.half()
+            buf = A.item_fault(clean, fault, arg, slots, mode, H, hd, 1)
+            assert fault in ("drop_item", "repeat_item_skip_next") or not bool(buf[:B].isnan().any())   # (the others leave no prefill)
+            seen[name] = _refusals(buf, case, check, B)
+        assert seen["qk"], f"{sid} {fault} {arg}: the QK selector passed a misplaced item"
+        assert "rel" not in seen or seen["rel"], f"{sid} {fault} {arg}: the rel-pos selector passed a misplaced item"
+        if fault == "drop_item":
+            assert all("NaN prefill" in v for v in seen.values()), (sid, fault, arg, seen)
+        if fault == "swap_heads":
+            assert seen["const"] == ["check_constant_v"], (sid, fault, arg, seen)
+        if fault == "repeat_item_skip_next" and arg == (B - 1, H - 1, R - 1):
+            assert all("guard rows" in v for v in seen.values()), (sid, fault, arg, seen)
+        lines.append(f"  {fault} {arg}: " + "; ".join(f"{k}: {', '.join(v) or 'passes (blind)'}" for k, v in seen.items()))
+    print(f"{sid}: {len(faults)} item faults, every one refused\n" + "\n".join(lines))
+
+
+def test_item_faults_through_reference():
+    """`reference(fault=...)` places the same faults: one small shape per mode, against `item_fault` on the sound result."""
+    for mode, geo in ((0, dict(N=200)), (2, dict(gh=20, gw=20))):
+        case = A.selector_qk(mode, 2, 3, 64, seed=41, **geo)
+        kw = dict(budget=False, item_rows=128, **A.ref_kwargs(case))
+        sound = A.reference(case.qkv, mode, **kw).o
+        slots = A.item_slots(mode, case.N, case.gh, case.gw, 128)
+        for fault, arg in (("drop_item", (1, 2, 1)), ("swap_heads", (0, 0, 2)), ("wrong_image", (1, 1, 0)),
+                           ("repeat_item_skip_next", (1, 2, slots.shape[0] - 1))):
+            got = A.reference(case.qkv, mode, fault=fault, fault_arg=arg, guard=1, **kw).o
+            want = A.item_fault(sound, fault, arg, slots, mode, 3, 64, 1)
+            assert got.shape == (3, case.N, 3 * 64) and torch.equal(got.isnan(), want.isnan())
+            assert torch.equal(got.nan_to_num(0.0), want.nan_to_num(0.0))
+            assert not torch.equal(got.nan_to_num(0.0), torch.cat([sound, torch.zeros_like(sound[:1])]))      # (the fault did something)

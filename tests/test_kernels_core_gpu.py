@@ -624,21 +624,31 @@ def test_attention_softmax_variants_agree(dev, mode, N, H, hd, B):
         kw = dict(mode=1, rel_h=rel_h, rel_w=rel_w, gh=gh, gw=g)
         rel = (rel_h[..., :gh].reshape(B, H, N, gh, 1) + rel_w.view(B, H, N, 1, g)).reshape(B, H, N, N)
     outs = []
-    # round-1 serial softmax, V2 on the register-staged kernel, V2 on the DMA-fed HIP kernel (gattn_kernel), the default: the assembly
-    # kernels of csrc/gattn_asm_gen.py where they apply (rel-pos, hd = 80 / 64, B * H a multiple of 8, N a multiple of 256)
-    for v in (0, 9, 17, 1):
+    # variant 0 (bit 0 clear, no kernel forced): the round-1 serial softmax ONLY where no assembly kernel applies - the kernel report
+    # showed it on the assembly kernels at every shape here but (0, 200, 3, 80); V2 on the register-staged kernel; V2 on the DMA-fed
+    # HIP kernel (gattn_kernel); the default: the assembly kernels of csrc/gattn_asm_gen.py where they apply (rel-pos: hd = 80 / 64, N a
+    # multiple of 256; no bias: hd = 64, N >= 128), else gattn_kernel; and variant 8, which does run the serial softmax (attn_kernel
+    # forced, bit 0 clear) at every shape - what variant 0 was meant to be. Each launch says which kernel it was.
+    full = ops.ATTN_KERNEL_FULL if N % 64 == 0 else 0
+    asm = (ops.ATTN_KERNEL_ASM_REL if N % 256 == 0 else 0) if mode == 1 else (ops.ATTN_KERNEL_ASM_NOREL if hd == 64 and N >= 128 else 0)
+    lands = {0: asm or ops.ATTN_KERNEL_ATTN | full, 9: ops.ATTN_KERNEL_ATTN | full | ops.ATTN_KERNEL_V2,
+             17: ops.ATTN_KERNEL_GATTN | full, 1: asm or ops.ATTN_KERNEL_GATTN | full, 8: ops.ATTN_KERNEL_ATTN | full}
+    for v in (0, 9, 17, 1, 8):
         ops.attention_set_variant(v)
         try:
             outs.append(ops.attention(qkv, B, N, H, hd, scale, **kw).float())
+            got = ops.attention_last_kernel()
         finally:
             ops.attention_set_variant(5)
+        assert got == lands[v], (v, ops.attention_kernel_name(got), ops.attention_kernel_name(lands[v]))
     ref = _ref_attn_global(qkv, B, N, H, hd, scale, rel=rel)
-    print(f"mode {mode} N={N} H={H} hd={hd} B={B}: max err vs fp32 reference of variants 0 / 9 / 17 / default: "
+    print(f"mode {mode} N={N} H={H} hd={hd} B={B}: max err vs fp32 reference of variants 0 / 9 / 17 / default / 8: "
           + ", ".join(f"{(o - ref).abs().max().item():.2e}" for o in outs))
     for o in outs:
         assert torch.isfinite(o).all()
         torch.testing.assert_close(o, ref, rtol=2e-3, atol=2e-3)
     assert (outs[0] - outs[1]).abs().max().item() < 2e-3
+    assert (outs[4] - outs[1]).abs().max().item() < 2e-3          # the serial softmax against V2 on the same kernel
 
 
 @pytest.mark.parametrize("N,H,B", [(1297, 12, 2), (1301, 16, 1), (2594, 12, 1), (5330, 12, 1), (128, 2, 1), (192, 3, 3), (320, 1, 9), (449, 5, 2)])
