@@ -577,6 +577,64 @@ def gattn_asm_admits(B, H):
     return 1 <= H <= 64 and B * H < 65536 // H
 
 
+# ---- the host-built work tables of the assembly kernels (csrc/work_tables.h), restated: tests/test_work_tables_cpu.py compares them
+# with the C++ entry for entry, tests/test_attention_items_gpu.py names the branches a case exercises from them --------------------------
+XCDS = 8                                   # as the kernels assume (workgroup wg on XCD wg & 7)
+NWIN64 = 25                                # 14 x 14 windows of the 64 x 64 map
+
+
+def wattn_shares(B, H, nwin, grid):
+    """per workgroup of wattn_p_kernel (and of wattn_work_list where it cuts contiguous shares): (wg, x, sx, nwg_x, windows of the
+    XCD, it0, it1)."""
+    ngrp = B * nwin
+    for wg in range(grid):
+        x, sx = wg & 7, wg >> 3
+        nwg_x = (grid + 7 - x) >> 3
+        nwin_x = (ngrp + 7 - x) >> 3
+        cnt_x = nwin_x * H
+        yield wg, x, sx, nwg_x, nwin_x, sx * cnt_x // nwg_x, (sx + 1) * cnt_x // nwg_x
+
+
+def wattn_asm_lists(B, H, grid):
+    """wattn_work_list of psam_wattn_asm_80 (the 64 x 64 map: 25 windows): per workgroup its list of (b, h, window), and whether it
+    keeps one head and strides over the windows (nwg_x % H == 0) or takes a contiguous share."""
+    nwin = NWIN64
+    lists, one_head = [], []
+    for wg, x, sx, nwg_x, nwin_x, it0, it1 in wattn_shares(B, H, nwin, grid):
+        if nwg_x % H == 0:
+            lanes, hh, lane = nwg_x // H, sx % H, sx // H
+            l = [(q, hh) for q in range(lane, nwin_x, lanes)]
+        else:
+            l = [divmod(i, H) for i in range(it0, it1)]
+        one_head.append(nwg_x % H == 0)
+        lists.append([((q * 8 + x) // nwin, h, (q * 8 + x) % nwin) for q, h in l])
+    return lists, one_head
+
+
+def gattn_asm_table(BH, nqb, xcds=XCDS):
+    """gattn_work_table: BH * nqb items cut into `xcds` equal runs, padded with -1, an entry (b * H + h) << 10 | query block."""
+    items = BH * nqb
+    per = -(-items // xcds)
+    tab = [-1] * (per * xcds)
+    for x in range(xcds):
+        i0, i1 = items * x // xcds, items * (x + 1) // xcds
+        for i in range(i0, i1):
+            tab[(i - i0) * xcds + x] = ((i // nqb) << 10) | (i % nqb)
+    return tab
+
+
+def gattn_asm_decode(tab, H):
+    """the kernels' decode of the table's entries, b = (grp * ceil(2^16 / H)) >> 16: the list of (b, h, query block)."""
+    M = (65536 + H - 1) // H
+    out = []
+    for e in tab:
+        if e >= 0:
+            grp, qb = e >> 10, e & 0x3ff
+            b = (grp * M) >> 16
+            out.append((b, grp - b * H, qb))
+    return out
+
+
 def item_shapes_cpu():
     """(mode, B, H, hd, N, gh, gw, item_rows) of the sweeps that the CPU can afford: tests/test_attention_reference_cpu.py injects
     the item faults at each. item_rows: 256 queries per item in the assembly kernels, 128 in the HIP global kernels."""

@@ -25,11 +25,9 @@
 // Rel-pos bias uses the UNSCALED q (image_encoder.py:242-245): rel_h/rel_w are produced by
 // psam_relpos from the same fp16 q and added in fp32 after the scale.
 #include "common.h"
+#include "device_tables.h"
 #include <stdlib.h>
-#include <map>
 #include <type_traits>
-#include <utility>
-#include <vector>
 
 struct AttnArgs {
   const half_t* qkv;      // [B, N, 3, H, HD]
@@ -1951,36 +1949,6 @@ struct GattnAsmArgs {
   int spare1, nvalid; const int* tab;
 };
 static_assert(sizeof(GattnAsmArgs) == 96, "kernarg layout of gattn_asm_gen.py");
-// Work table of the global kernels, per device and (B * H, query blocks): entry wg = (b * H + h) << 10 | query block, -1 = none.
-// Workgroup wg runs on XCD wg % 8 (observed placement, speed only): the (b, h)-major item list is cut into eight equal contiguous
-// runs, XCD x walks run x - the same number of workgroups on every XCD, and the ones of an XCD that run side by side read the same
-// K / V. (12 heads x 21 query blocks of one 1022^2 DINOv2 image: 252 items = one round of 256 CUs; the arithmetic map of round 4
-// - eight (b, h) pairs per row of XCDs - ran it in two.)
-struct GattnTable { int* dev; int grid; };
-static std::map<unsigned long long, GattnTable> g_gattn_tabs;
-static const GattnTable* gattn_worklist(int BH, int nqb) {
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  int cus, xcds;
-  psam_device_geometry(&cus, &xcds);
-  if (xcds < 1 || xcds > 64) xcds = 8;
-  const unsigned long long key = ((unsigned long long)BH << 32) | ((unsigned long long)nqb << 16) | ((unsigned long long)xcds << 8) | (unsigned)dev;
-  auto it = g_gattn_tabs.find(key);
-  if (it != g_gattn_tabs.end()) return &it->second;
-  const long long items = (long long)BH * nqb;
-  const int per = (int)((items + xcds - 1) / xcds);
-  std::vector<int> h((size_t)per * xcds, -1);
-  for (int x = 0; x < xcds; ++x) {
-    const long long i0 = items * x / xcds, i1 = items * (x + 1) / xcds;
-    for (long long i = i0; i < i1; ++i) h[(size_t)(i - i0) * xcds + x] = (int)(((i / nqb) << 10) | (i % nqb));
-  }
-  GattnTable t;
-  t.grid = per * xcds;
-  t.dev = nullptr;
-  if (hipMalloc((void**)&t.dev, h.size() * sizeof(int)) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-  if (hipMemcpy(t.dev, h.data(), h.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(t.dev); return nullptr; }
-  return &(g_gattn_tabs[key] = t);
-}
 // kind: 0 rel (tables from HBM), 1 fused (tables computed in the kernel), 2 norel
 static bool gattn_asm_eligible(const AttnArgs& p, int mode, int hd, int kind) {
   if (kind == 2) { if (mode != 0 || hd != 64 || p.N < 128) return false; }
@@ -2001,7 +1969,9 @@ static int launch_gattn_asm(const AttnArgs& p, hipStream_t s, int hd, int kind) 
   const int nqb = (p.N + 255) / 256;
   a.qkv = p.qkv; a.out = p.out;
   a.rel_h = kind == 1 ? (const void*)p.rpack : (const void*)p.rel_h; a.rel_w = p.rel_w;
-  const GattnTable* tab = gattn_worklist(p.B * p.H, nqb);
+  int xcds = psam_device_geometry().xcds;
+  if (xcds < 1 || xcds > 64) xcds = 8;
+  const PsamDeviceTable* tab = psam_device_table(PSAM_TAB_GATTN, {p.B * p.H, nqb, xcds});   // gattn_work_table: -1 = no item
   if (!tab) return PSAM_ERR_LAUNCH;
   a.N = p.N; a.H = p.H;
   a.spare0 = 0;
@@ -2011,7 +1981,7 @@ static int launch_gattn_asm(const AttnArgs& p, hipStream_t s, int hd, int kind) 
   a.NT = (p.N + 63) / 64; a.orow = p.H * hd * 2;
   a.rwmul = 1.0f / p.scale;      // rel_w is staged as rel_w / scale: it enters the score MFMAs as their accumulator input
   a.BH = p.B * p.H;              // workgroups of the groups beyond it (the grid is rounded up to eight (b, h) per row of XCDs) leave at once
-  a.spare1 = 0; a.nvalid = p.N - (a.NT - 1) * 64; a.tab = tab->dev;
+  a.spare1 = 0; a.nvalid = p.N - (a.NT - 1) * 64; a.tab = (const int*)tab->dev;
   size_t sz = sizeof(a);
   void* extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
   const int grid = tab->grid;
@@ -2034,91 +2004,19 @@ static bool wattn_asm_eligible(const AttnArgs& p, int hd) {
   if (p.hs != hd || p.ws_ != (long long)p.H * hd || p.ts != 3LL * p.H * hd) return false;      // token-major packed qkv
   return p.B <= 255 && p.H <= 255 && (long long)p.N * p.ts * 2 < 0x20000000LL;
 }
-// Host tables of the kernel, built once per device: (a) DMA geometry - per (image kind, piece of 64 lanes, lane) the byte offset of
-// the lane's 16-byte chunk relative to the window's first token, its offset inside a pad row, and per edge class (partial last
-// window row / column) the exec masks "token row" / "pad row" of every piece; (b) the work list - per workgroup its (image, head,
-// window) items in the XCD-aware order of wattn_p_kernel (windows of one XCD together, the heads of a window back to back).
-// (one geometry table per row stride, never rewritten once published: launches already enqueued and captured graphs keep its address)
-struct WattnTables { std::map<long long, unsigned*> geoms; std::map<unsigned long long, std::pair<int*, int>> work; };
-static std::map<int, WattnTables> g_wattn_tabs;
-static const unsigned* wattn_geometry(WattnTables& t, long long rs2) {
-  { auto it = t.geoms.find(rs2); if (it != t.geoms.end()) return it->second; }
-  constexpr int P = 42, NP = 35, WS = 14, GWID = 64;
-  std::vector<unsigned> h((size_t)3 * P * 64 + (size_t)4 * 2 * P * 4, 0u);
-  for (int img = 0; img < 2; ++img)
-    for (int pc = 0; pc < NP; ++pc)
-      for (int l = 0; l < 64; ++l) {
-        const int S = pc * 64 + l, R = S / 10, c = S - R * 10;
-        int ky, kx;
-        if (img == 0) { ky = R >> 4; kx = R & 15; }
-        else { const int C = R >> 5, rho = R & 31; ky = 2 * C + ((rho >> 3) & 1); kx = 4 * (2 * (rho >> 4) + ((rho >> 2) & 1)) + (rho & 3); }
-        const bool valid = kx < WS && ky < WS;
-        h[((size_t)img * P + pc) * 64 + l] = valid ? (unsigned)((long long)(ky * GWID + kx) * rs2 + c * 16) : 0u;
-        h[((size_t)2 * P + pc) * 64 + l] = (unsigned)(c * 16);
-        for (int cls = 0; cls < 4; ++cls) {
-          const bool ey = cls & 2, ex = cls & 1;
-          const bool in = valid && !(ey && ky >= 8) && !(ex && kx >= 8), pad = valid && !in;
-          unsigned* m = &h[(size_t)3 * P * 64 + (((size_t)cls * 2 + img) * P + pc) * 4];
-          if (in) m[l >> 5] |= 1u << (l & 31);
-          if (pad) m[2 + (l >> 5)] |= 1u << (l & 31);
-        }
-      }
-  unsigned* g = nullptr;
-  if (hipMalloc((void**)&g, h.size() * 4) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-  if (hipMemcpy(g, h.data(), h.size() * 4, hipMemcpyHostToDevice) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(g); return nullptr; }
-  return t.geoms[rs2] = g;
-}
-static const int* wattn_worklist(WattnTables& t, int B, int H, int grid) {
-  const unsigned long long key = ((unsigned long long)B << 40) | ((unsigned long long)H << 20) | (unsigned)grid;
-  auto it = t.work.find(key);
-  if (it != t.work.end()) return it->second.first;
-  const int nwin = 25, ngrp = B * nwin;
-  std::vector<std::vector<int>> lists(grid);
-  size_t rows = 0;
-  for (int wg = 0; wg < grid; ++wg) {
-    const int x = wg & 7, sx = wg >> 3;
-    const int nwg_x = (grid + 7 - x) >> 3;
-    const int nwin_x = (ngrp + 7 - x) >> 3;        // windows (b, wy, wx) of XCD x: grp = q * 8 + x
-    auto push = [&](int grpq, int hh) {
-      const int grp = grpq * 8 + x, win = grp % nwin, b = grp / nwin;
-      lists[wg].push_back(b | (hh << 8) | ((win / 5) << 16) | ((win % 5) << 24));
-    };
-    if (nwg_x % H == 0) {
-      // the workgroups of an XCD that run side by side take the H heads of the SAME window(s): a token's q / k / v rows of adjacent
-      // heads are 160-byte neighbours, i.e. they share 128-byte lines - fetched once into the XCD's L2 instead of once per head
-      // (measured, 16 slices: FETCH_SIZE 834 -> see DESIGN.md; a workgroup keeps ONE head and walks the windows)
-      const int lanes = nwg_x / H, hh = sx % H, lane = sx / H;
-      for (int q = lane; q < nwin_x; q += lanes) push(q, hh);
-    } else {
-      const long long cnt_x = (long long)nwin_x * H;
-      const int it0 = (int)((long long)sx * cnt_x / nwg_x), it1 = (int)((long long)(sx + 1) * cnt_x / nwg_x);
-      for (int i = it0; i < it1; ++i) push(i / H, i % H);
-    }
-    rows = lists[wg].size() > rows ? lists[wg].size() : rows;
-  }
-  rows += 2;
-  std::vector<int> h(rows * grid, -1);
-  for (int wg = 0; wg < grid; ++wg)
-    for (size_t i = 0; i < lists[wg].size(); ++i) h[i * grid + wg] = lists[wg][i];
-  int* dev = nullptr;
-  if (hipMalloc((void**)&dev, h.size() * 4) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-  if (hipMemcpy(dev, h.data(), h.size() * 4, hipMemcpyHostToDevice) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-  t.work[key] = std::make_pair(dev, (int)rows);
-  return dev;
-}
+// Host tables of the kernel (work_tables.h, uploaded once per device by device_tables.h): the DMA geometry per row stride
+// (wattn_geometry_table) and the work list per (B, H, grid) (wattn_work_list).
 static int launch_wattn_asm(const AttnArgs& p, hipStream_t s) {
   hipFunction_t f = psam_asm_function("psam_wattn_asm_80");
   if (!f) return PSAM_ERR_LAUNCH;
-  int cus, xcds, dev = 0;
-  psam_device_geometry(&cus, &xcds);
-  (void)hipGetDevice(&dev);
-  WattnTables& t = g_wattn_tabs[dev];
-  const int nitems = p.B * p.nwin * p.H;
+  const int cus = psam_device_geometry().cus, nitems = p.B * p.nwin * p.H;
   const int grid = nitems < cus ? nitems : cus;
+  const PsamDeviceTable* geom = psam_device_table(PSAM_TAB_WATTN_GEOM, {p.ts * 2});
+  const PsamDeviceTable* work = psam_device_table(PSAM_TAB_WATTN_WORK, {p.B, p.H, grid});
+  if (!geom || !work) return PSAM_ERR_LAUNCH;
   WattnAsmArgs a;
-  a.geom = wattn_geometry(t, p.ts * 2);
-  a.work = wattn_worklist(t, p.B, p.H, grid);
-  if (!a.geom || !a.work) return PSAM_ERR_LAUNCH;
+  a.geom = (const unsigned*)geom->dev;
+  a.work = (const int*)work->dev;
   a.qkv = p.qkv; a.out = p.out; a.rpack = p.rpack; a.pad_row = p.pad_row;
   a.N = p.N; a.H = p.H; a.rs2 = (int)(p.ts * 2); a.hs2 = (int)(p.hs * 2); a.ws2 = (int)(p.ws_ * 2); a.orow = p.H * 80 * 2; a.G = grid;
   a.sl2 = p.scale * 1.4426950408889634f; a.isc = 1.0f / p.scale; a.pad0 = a.pad1 = a.pad2 = 0;
@@ -2142,9 +2040,7 @@ static int launch_attn(AttnArgs p, int mode, hipStream_t s) {
     if (g_wattn < 0) { const char* e = getenv("PSAM_WATTN"); g_wattn = e ? atoi(e) : 2; }
     if (g_wattn == 2 && wattn_asm_eligible(p, HD)) return launch_wattn_asm(p, s);
     if (g_wattn >= 2 && p.rpack != nullptr) {
-      int cus, xcds;
-      psam_device_geometry(&cus, &xcds);
-      const int nitems = p.B * p.nwin * p.H;
+      const int cus = psam_device_geometry().cus, nitems = p.B * p.nwin * p.H;
       g_last_kernel = AK_WATTN_P;
       hipLaunchKernelGGL((wattn_p_kernel<HD>), dim3(nitems < cus ? nitems : cus), dim3(14 * 64), 0, s, p, nitems);
       return psam_launch_status();

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "work_tables.h"   // xcd_remap, tile_map and the host-built work tables: plain C++, no HIP
 
 typedef _Float16 half_t;
 typedef _Float16 half2_t __attribute__((ext_vector_type(2)));
@@ -22,20 +23,6 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 static inline int psam_launch_status() {
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? PSAM_OK : PSAM_ERR_LAUNCH;
-}
-
-// CU / XCD counts of the current device, read once per translation unit (persistent grids, XCD-aware maps)
-static inline void psam_device_geometry(int* cus, int* xcds) {
-  static int g_cus = 0, g_xcds = 0;
-  if (g_cus == 0) {
-    int dev = 0, v = 0;
-    (void)hipGetDevice(&dev);
-    g_cus = (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ? v : 256;
-    g_xcds = (hipDeviceGetAttribute(&v, hipDeviceAttributeNumberOfXccs, dev) == hipSuccess && v > 0) ? v : 8;
-    (void)hipGetLastError();
-  }
-  *cus = g_cus;
-  *xcds = g_xcds;
 }
 
 __device__ __forceinline__ float wave_sum(float v) {
@@ -69,14 +56,4 @@ __device__ __forceinline__ float gelu_erf(float x) {
   const float y = fmaf(-poly * t, e, 1.0f);                                         // |erf(x / sqrt(2))|
   const float h = 0.5f * x;
   return fmaf(h, copysignf(y, x), h);
-}
-
-// XCD-aware bijective block remap (8 XCDs; block b runs on XCD b % 8): gives each XCD a
-// contiguous chunk of the logical tile space so neighbouring tiles share an L2.
-__host__ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
-  const int nx = 8;
-  int xcd = bid % nx, idx = bid / nx;
-  int q = nwg / nx, r = nwg % nx;
-  int base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-  return base + idx;
 }

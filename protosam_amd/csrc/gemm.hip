@@ -19,6 +19,7 @@
 // (slot ^= (row>>1)&7) that makes the ds_read_b128 fragment reads bank-conflict-free is applied on
 // the DMA's per-lane SOURCE address, because the LDS side of the DMA is lane-linear.
 #include "common.h"
+#include "device_tables.h"
 #include "gemm_asm_meta.h"   // generated: PSAM_ASM2_E_* (gemm_asm_gen.py --meta)
 #include <stdlib.h>
 #include <string.h>
@@ -63,24 +64,10 @@ struct GemmArgs {
 };
 
 
-// ---- device geometry, read once from the runtime (a full MI355X reports 256 CUs in 8 XCDs; a CPX / NPS partition fewer) ----
-// The XCD-region tile maps below are written for 8 XCDs (block b on XCD b % 8, observed placement, speed only): on any other
+// ---- device geometry (device_tables.h: per DEVICE; every cache here that holds device-side state is keyed by hipGetDevice()) ----
+// The XCD-region tile maps (work_tables.h) are written for 8 XCDs (block b on XCD b % 8, observed placement, speed only): on any other
 // geometry the launchers fall back to the identity map, and the persistent grids / fill tests use the real CU count.
-// (per DEVICE: one process may drive several GPUs; every cache below that holds device-side state is keyed by hipGetDevice())
-struct DevGeom { int cus = 0, xcds = 0; };
-static DevGeom g_geom[64];
-static inline int cur_device() { int dev = 0; (void)hipGetDevice(&dev); return dev; }
-static const DevGeom& device_geometry() {
-  const int dev = cur_device();
-  DevGeom& g = g_geom[dev & 63];
-  if (g.cus > 0) return g;
-  int v = 0;
-  g.cus = (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ? v : 256;
-  g.xcds = (hipDeviceGetAttribute(&v, hipDeviceAttributeNumberOfXccs, dev) == hipSuccess && v > 0) ? v : 8;
-  (void)hipGetLastError();
-  return g;
-}
-static inline int num_cus() { return device_geometry().cus; }
+static inline int num_cus() { return psam_device_geometry().cus; }
 // Cap on the persistent grids (psam_gemm_set_option("max_wgs", n) / PSAM_GEMM_MAX_WGS; 0 = none): with half the CUs per launch, two
 // streams run their GEMMs side by side on disjoint CUs (one's epilogue traffic beside the other's k-loops)
 static int g_max_wgs = -1;
@@ -89,91 +76,14 @@ static inline int eff_cus() {
   const int n = num_cus();
   return (g_max_wgs > 0 && g_max_wgs < n) ? g_max_wgs : n;
 }
-static inline bool xcd_maps_apply() { const DevGeom& g = device_geometry(); return g.xcds == 8 && g.cus % 8 == 0; }
-
-// ---- tile -> workgroup mapping ------------------------------------------------------------------------------------
-// Block b runs on XCD b % 8 (observed placement; used for speed only, never for correctness) and every XCD has a
-// private 4 MiB L2. The tiles an XCD works on CONCURRENTLY (32 CUs x blocks/CU) should therefore share as many A row
-// panels and W column panels as possible: the 8 XCDs are laid out as an xm x xn grid over the tile space (the split
-// that minimises rows + cols per region) and each XCD walks its region in 4-row strips, column by column, so any 32
-// consecutive tiles of an XCD form a ~4 x 8 patch (12 operand panels instead of 33 for a row-major chunk).
-// Measured on 8192^3 (256x256 tiles): DMA-only time 1213 us (contiguous chunk per XCD) -> 500 us (2-D spread).
-__host__ __device__ __forceinline__ bool tile_map(int bid, int ntm, int ntn, int mode, int& tm, int& tn) {
-  if (mode == 1) {
-    if (bid >= ntm * ntn) return false;
-    tm = bid / ntn;
-    tn = bid % ntn;
-    return true;
-  }
-  if (mode == 2) {
-    if (bid >= ntm * ntn) return false;
-    const int t = xcd_remap(bid, ntm * ntn);
-    tm = t / ntn;
-    tn = t % ntn;
-    return true;
-  }
-  const int xcd = bid & 7, idx = bid >> 3;
-  int xm = 8, xn = 1, best = (ntm + 7) / 8 + ntn;
-  {
-    int c = (ntm + 3) / 4 + (ntn + 1) / 2;
-    if (c < best) { best = c; xm = 4; xn = 2; }
-    c = (ntm + 1) / 2 + (ntn + 3) / 4;
-    if (c < best) { best = c; xm = 2; xn = 4; }
-    c = ntm + (ntn + 7) / 8;
-    if (c < best) { best = c; xm = 1; xn = 8; }
-  }
-  // proportional (balanced) split: region rx owns rows [rx*ntm/xm, (rx+1)*ntm/xm)
-  const int rx = xcd / xn, cx = xcd % xn;
-  const int r0 = (rx * ntm) / xm, c0 = (cx * ntn) / xn;
-  const int nr = ((rx + 1) * ntm) / xm - r0, nc = ((cx + 1) * ntn) / xn - c0;
-  if (nr <= 0 || nc <= 0 || idx >= nr * nc) return false;
-  const int strip = idx / (4 * nc), rem = idx - strip * 4 * nc;
-  const int rows = (nr - strip * 4) < 4 ? (nr - strip * 4) : 4;
-  tm = r0 + strip * 4 + rem % rows;
-  tn = c0 + rem / rows;
-  return true;
-}
-// Largest number of tiles any XCD region of the 2-D map (mode 0) holds (host side). One workgroup per CU and 32 CUs per
-// XCD: a region of 33 tiles costs two rounds where a balanced split costs one (85 x 3 tiles: five regions of 11 x 3).
-static int tile_map_max_region(int ntm, int ntn) {
-  int xm = 8, xn = 1, best = (ntm + 7) / 8 + ntn;
-  int c = (ntm + 3) / 4 + (ntn + 1) / 2;
-  if (c < best) { best = c; xm = 4; xn = 2; }
-  c = (ntm + 1) / 2 + (ntn + 3) / 4;
-  if (c < best) { best = c; xm = 2; xn = 4; }
-  c = ntm + (ntn + 7) / 8;
-  if (c < best) { best = c; xm = 1; xn = 8; }
-  int mx = 0;
-  for (int x = 0; x < 8; ++x) {
-    const int rx = x / xn, cx = x % xn;
-    const int nr = ((rx + 1) * ntm) / xm - (rx * ntm) / xm, nc = ((cx + 1) * ntn) / xn - (cx * ntn) / xn;
-    mx = nr * nc > mx ? nr * nc : mx;
-  }
-  return mx;
-}
-// map for the one-workgroup-per-CU kernels: the 2-D region map unless its fullest region needs more rounds than a balanced
-// split of the tiles (then contiguous, balanced chunks per XCD: mode 2). PSAM_GEMM_MAP overrides.
+static inline bool xcd_maps_apply() { const PsamDevGeom& g = psam_device_geometry(); return g.xcds == 8 && g.cus % 8 == 0; }
+// map for the one-workgroup-per-CU kernels: pick_map_mode of work_tables.h on this device. PSAM_GEMM_MAP overrides.
 static int pick_map_mode(int ntm, int ntn) {
   static int forced = -2;
   if (forced == -2) { const char* e = getenv("PSAM_GEMM_MAP"); forced = e ? atoi(e) : -1; }
   if (forced >= 0) return forced;
-  if (!xcd_maps_apply()) return 1;   // not the 8-XCD geometry the region maps are laid out for: identity
-  const int total = ntm * ntn, ncu = num_cus(), per_xcd = ncu / 8;
-  const int rounds_region = (tile_map_max_region(ntm, ntn) + per_xcd - 1) / per_xcd, rounds_even = (total + ncu - 1) / ncu;
-  return rounds_region > rounds_even ? 2 : 0;
-}
-// grid size that covers every region of tile_map (host side)
-static int tile_map_grid(int ntm, int ntn, int mode) {
-  if (mode != 0) return ntm * ntn;
-  int xm = 8, xn = 1, best = (ntm + 7) / 8 + ntn;
-  int c = (ntm + 3) / 4 + (ntn + 1) / 2;
-  if (c < best) { best = c; xm = 4; xn = 2; }
-  c = (ntm + 1) / 2 + (ntn + 3) / 4;
-  if (c < best) { best = c; xm = 2; xn = 4; }
-  c = ntm + (ntn + 7) / 8;
-  if (c < best) { best = c; xm = 1; xn = 8; }
-  const int R = (ntm + xm - 1) / xm, Cc = (ntn + xn - 1) / xn;
-  return 8 * R * Cc;
+  const PsamDevGeom& g = psam_device_geometry();
+  return pick_map_mode(ntm, ntn, g.cus, g.xcds);
 }
 
 // Epilogue for one 32x32 accumulator computed as D^T = W_frag . X_frag^T (weights as the MFMA A operand): lane holds
@@ -1323,7 +1233,7 @@ extern "C" int psam_gemm_asm_variant(int v) {
   return PSAM_OK;
 }
 static AsmModule* asm_module() {
-  AsmModule& m = g_asm[cur_device()];
+  AsmModule& m = g_asm[psam_current_device()];
   if (m.state == 0) {
     m.state = -1;
     const char* path = getenv("PSAM_GEMM_ASM_CO");          // (experiments: a code object built from another schedule)
@@ -1369,46 +1279,6 @@ hipFunction_t psam_asm_function(const char* name) {
   hipFunction_t f = nullptr;
   if (hipModuleGetFunction(&f, m->mod, name) != hipSuccess) { (void)hipGetLastError(); f = nullptr; }
   return m->named[name] = f;
-}
-struct AsmTable { int grid; int* dev; };
-static std::map<unsigned long long, AsmTable> g_asm_tabs;
-// work list of workgroup b: entry i at tab[i * G + b] = tm | tn << 16, terminated (and padded two rows deep) by -1
-// halves > 0 (tile 16): every 256x256 tile of the map becomes its 256x128 halves (tm, 2 tn), (tm, 2 tn + 1) back to back - they share
-// the A panel - and `halves` is the number of 128-column blocks of the matrix (the last tile column may have one)
-static const AsmTable* asm_table(int ntm, int ntn, int mode, int halves = 0, int wg_per_cu = 1) {
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (ntm >= 4096 || ntn >= (1 << 20)) return nullptr;   // (the key's fields: 12 bits of ntm below the CU count)
-  const unsigned long long key = ((unsigned long long)eff_cus() << 52) | ((unsigned long long)ntm << 40) | ((unsigned long long)ntn << 20) | ((unsigned long long)(halves ? 1 : 0) << 19) |
-                                 ((unsigned long long)(halves & 1) << 18) | ((unsigned long long)(wg_per_cu - 1) << 16) | ((unsigned long long)mode << 8) | (unsigned)dev;
-  auto it = g_asm_tabs.find(key);
-  if (it != g_asm_tabs.end()) return &it->second;
-  const int total = tile_map_grid(ntm, ntn, mode);
-  const int G = total < eff_cus() * wg_per_cu ? total : eff_cus() * wg_per_cu;
-  std::vector<std::vector<int>> lists(G);
-  for (int b = 0; b < G; ++b)
-    for (int idx = b; idx < total; idx += G) {
-      int tm = 0, tn = 0;
-      if (!tile_map(idx, ntm, ntn, mode, tm, tn)) continue;
-      if (!halves) { lists[b].push_back(tm | (tn << 16)); continue; }
-      lists[b].push_back(tm | ((2 * tn) << 16));
-      if (2 * tn + 1 < halves) lists[b].push_back(tm | ((2 * tn + 1) << 16));
-    }
-  size_t rows = 0;
-  for (auto& l : lists) rows = l.size() > rows ? l.size() : rows;
-  rows += 3;
-  std::vector<int> h(rows * G, -1);
-  for (int b = 0; b < G; ++b)
-    for (size_t i = 0; i < lists[b].size(); ++i) h[i * G + b] = lists[b][i];
-  AsmTable t;
-  t.grid = G;
-  t.dev = nullptr;
-  if (hipMalloc((void**)&t.dev, h.size() * sizeof(int)) != hipSuccess) return nullptr;
-  if (hipMemcpy(t.dev, h.data(), h.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) {
-    (void)hipFree(t.dev);                                   // (nothing is cached: a retry allocates again)
-    return nullptr;
-  }
-  return &(g_asm_tabs[key] = t);
 }
 // lnf: 0 plain, 1 a folded-LayerNorm launch (tiles 15 and 17 have _ln forms of their kernels, tile 16 none)
 // family 3 (tile 17) takes exactly what family 1 (tile 15) takes
@@ -1456,7 +1326,8 @@ static int launch_asm(const GemmArgs& p, int epilogue, hipStream_t s, int family
   // family 2 walks 256x128 half-tiles in the same XCD-aware order: the workgroups of an XCD that run side by side then share A panels
   // (one workgroup doing both halves of a 256x256 tile back to back re-read its A panel from beyond the L2: measured 20 % slower on fc2)
   const int ntm = (p.M + 255) / 256, ntn = family == 2 ? p.N / 128 : p.N / 256;
-  const AsmTable* t = asm_table(ntm, ntn, pick_map_mode(ntm, ntn));
+  // the work list of workgroup b (gemm_work_table): entry i at tab[i * G + b] = tm | tn << 16, terminated by -1
+  const PsamDeviceTable* t = psam_device_table(PSAM_TAB_GEMM, {ntm, ntn, pick_map_mode(ntm, ntn), eff_cus()});
   if (!t) return PSAM_ERR_LAUNCH;
   AsmGemmArgs a;
   a.A = p.A; a.W = p.W; a.bias = p.bias; a.out = p.out; a.resid = p.resid; a.gamma = p.gamma; a.tab = t->dev;
@@ -1506,38 +1377,6 @@ static int launch_asm(const GemmArgs& p, int epilogue, hipStream_t s, int family
 // is safe inside a captured graph: nothing is shared between streams or graphs), then ONE pass that finishes the residual update
 // AND the LayerNorm that follows it in the block stack: x += bias + sum_r plane_r (fixed order: deterministic), out16 = LN(x) - the
 // separate LayerNorm pass of the one-slice path disappears. modeling/common.py:13-26 + image_encoder.py:174-193.
-static const AsmTable* asm_table_splitk(int ntm, int ntn, int ks) {
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (ntm >= 4096 || ntn >= (1 << 16) || ks < 2 || ks > 8) return nullptr;
-  const unsigned long long key = (1ull << 63) | ((unsigned long long)eff_cus() << 52) | ((unsigned long long)ntm << 40) | ((unsigned long long)ntn << 20) |
-                                 ((unsigned long long)ks << 8) | (unsigned)dev;
-  auto it = g_asm_tabs.find(key);
-  if (it != g_asm_tabs.end()) return &it->second;
-  const int mode = pick_map_mode(ntm, ntn);
-  const int ntiles = tile_map_grid(ntm, ntn, mode);
-  std::vector<int> items;                                  // the ranges of a tile are neighbours: they share both operand panels' rows
-  for (int idx = 0; idx < ntiles; ++idx) {
-    int tm = 0, tn = 0;
-    if (!tile_map(idx, ntm, ntn, mode, tm, tn)) continue;
-    for (int r = 0; r < ks; ++r) items.push_back(tm | (r << 12) | (tn << 16));
-  }
-  const int total = (int)items.size();
-  const int G = total < eff_cus() ? total : eff_cus();
-  const size_t rows = (size_t)(total + G - 1) / G + 3;
-  std::vector<int> h(rows * G, -1);
-  for (int i = 0; i < total; ++i) h[(size_t)(i / G) * G + (i % G)] = items[i];
-  AsmTable t;
-  t.grid = G;
-  t.dev = nullptr;
-  if (hipMalloc((void**)&t.dev, h.size() * sizeof(int)) != hipSuccess) return nullptr;
-  if (hipMemcpy(t.dev, h.data(), h.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) {
-    (void)hipFree(t.dev);                                   // (nothing is cached: a retry allocates again)
-    return nullptr;
-  }
-  return &(g_asm_tabs[key] = t);
-}
-
 // x[M,N] (fp32, ldx) += bias + sum over the ks planes of ws ([ks][Mp][N] fp32, Mp = M rounded up to whole 256-row tiles) in the order r = 0, 1, ...; then, per row,
 // out16 = fp16(LayerNorm(x) * ln_w + ln_b) (two-pass mean / variance as layernorm_kernel) or fp16(x) when ln_w is null. One wave per
 // row, the row in registers. HBM: (ks + 1) * 4 N read, 4 N + 2 N written per row.
@@ -1610,20 +1449,15 @@ __global__ __launch_bounds__(256) void splitk_reduce_ln_kernel(const float* __re
 // How many K ranges psam_gemm_f16_splitk_ln would use for this shape on this device (0: the shape does not pay - few tiles AND a long K
 // are needed: every range keeps >= 16 K-tiles, the items fill >= 3/4 of the CUs in one round; or the assembly kernel is not loaded).
 extern "C" int psam_gemm_splitk_ranges(int M, int N, int K) {
-  if (M <= 0 || N <= 0 || K <= 0 || (N % 256) || (K % 64) || N > 64 * 4 * SKR_MAXV) return 0;
-  const int tiles = ((M + 255) / 256) * (N / 256), nkt = K / 64, ncu = eff_cus();
-  if (tiles * 2 > ncu) return 0;
-  int ks = ncu / tiles;
-  if (ks > 8) ks = 8;
-  while (ks >= 2 && nkt / ks < 16) --ks;
-  if (ks < 2 || tiles * ks * 4 < ncu * 3) return 0;
-  return psam_asm_function("psam_gemm_asm_f32_sk") ? ks : 0;
+  static_assert(SPLITK_MAX_N == 64 * 4 * SKR_MAXV, "splitk_reduce_ln_kernel holds a row of N floats in registers");
+  const int ks = splitk_ranges(M, N, K, eff_cus());
+  return ks && psam_asm_function("psam_gemm_asm_f32_sk") ? ks : 0;
 }
 
 // x[M,N] (fp32, in place) += A[M,K] . W[N,K]^T + bias; out16 (optional, fp16 [M, ld16]) = LayerNorm(x; ln_w, ln_b, eps), or fp16(x) when
 // ln_w is null. ws: caller-owned fp32 scratch of at least ks * Mp * N elements, Mp = M rounded up to a multiple of 256 (ks =
 // psam_gemm_splitk_ranges(M, N, K), which must be >= 2).
-// Deterministic. The first call per (M, N, ks) on a device builds the work list (asm_table_splitk: hipMalloc + hipMemcpy), so it must run
+// Deterministic. The first call per (M, N, ks) on a device builds and uploads the work list (splitk_work_table, device_tables.h), so it must run
 // outside stream capture; later calls of the shape touch no library-owned state and may be captured into a graph.
 extern "C" int psam_gemm_f16_splitk_ln(const void* A, const void* W, const float* bias, float* x, int M, int N, int K, int lda, int ldw,
                                        int ldx, int ks, float* ws, const float* ln_w, const float* ln_b, float eps, void* out16, int ld16,
@@ -1640,7 +1474,8 @@ extern "C" int psam_gemm_f16_splitk_ln(const void* A, const void* W, const float
   p.out16 = nullptr; p.ld16 = 0; p.stats = nullptr; p.ln_mr = nullptr; p.ln_s = nullptr; p.wide16 = false; p.ksplit = 1; p.ks_ws = nullptr;
   if (!asm_eligible(p, EPI_F32, 0) || (unsigned long long)ks * ((M + 255) & ~255) * N * 4 > 0xffffffffull) return PSAM_ERR_ARG;
   hipFunction_t fn = psam_asm_function("psam_gemm_asm_f32_sk");
-  const AsmTable* t = asm_table_splitk((M + 255) / 256, N / 256, ks);
+  const int ntm = (M + 255) / 256, ntn = N / 256;
+  const PsamDeviceTable* t = psam_device_table(PSAM_TAB_SPLITK, {ntm, ntn, pick_map_mode(ntm, ntn), ks, eff_cus()});
   if (!fn || !t) return PSAM_ERR_LAUNCH;
   AsmGemmArgs a;
   a.A = A; a.W = W; a.bias = nullptr; a.out = ws; a.resid = nullptr; a.gamma = nullptr; a.tab = t->dev;

@@ -3,14 +3,16 @@ batch and head counts the arithmetic tests (tests/test_attention_exact_gpu.py, B
 odd H, fewer items than XCDs, more items than CUs, both branches of the window kernel's work list and the last (B, H) the global
 assembly kernels' work table admits.
 
-The maps (csrc/attention.hip), restated on the host below so that every case can say which of their branches it exercises:
+The maps (csrc/attention.hip; the two host-built tables csrc/work_tables.h), restated on the host - below, and the list-building parts
+in oracle/attention.py, which tests/test_work_tables_cpu.py compares with the C++ - so that every case can say which of their branches
+it exercises:
   * attn_kernel, wattn_kernel, gattn_kernel, gattn_any_kernel: blockIdx.x -> group g * 8 + (r & 7), index r >> 3 over
     ceil(groups / 8) * 8 * per workgroups; those of a group >= groups leave at once (`_arith`);
   * wattn_p_kernel: min(B * windows * H, CUs) workgroups; XCD x = wg & 7 owns the windows grp = q * 8 + x, its workgroups cut its
     (window, head) list into contiguous shares and walk them with item_at / item_next (`_wattn_p_lists`);
-  * psam_wattn_asm_80: the host table wattn_worklist - where an XCD's workgroup count is a multiple of H a workgroup keeps ONE head and
+  * psam_wattn_asm_80: the host table wattn_work_list - where an XCD's workgroup count is a multiple of H a workgroup keeps ONE head and
     strides over the windows, elsewhere the contiguous shares of wattn_p_kernel (`_wattn_asm_lists`);
-  * psam_gattn_asm_*: the host table gattn_worklist - B * H * query blocks items cut into eight equal runs, padded with -1, an entry
+  * psam_gattn_asm_*: the host table gattn_work_table - B * H * query blocks items cut into eight equal runs, padded with -1, an entry
     (b * H + h) << 10 | query block, and b = ((b * H + h) * ceil(2^16 / H)) >> 16 inside the kernel (`_gattn_asm_table`).
 
 That division: with M = ceil(2^16 / H) = (2^16 + e) / H, 0 <= e < H, and grp = b H + h, 0 <= h < H:
@@ -40,8 +42,9 @@ from test_attention_exact_gpu import _any_id, _full, _relpos_id, _run   # noqa: 
 
 pytestmark = pytest.mark.gpu
 
-XCDS = 8                                   # as the kernels assume (blockIdx.x & 7)
-NWIN64 = 25                                # 14 x 14 windows of the 64 x 64 map
+XCDS = A.XCDS                              # as the kernels assume (blockIdx.x & 7)
+NWIN64 = A.NWIN64                          # 14 x 14 windows of the 64 x 64 map
+_shares = A.wattn_shares                   # per workgroup of wattn_p_kernel: (wg, x, sx, nwg_x, windows of the XCD, it0, it1)
 
 
 def _cus():
@@ -61,17 +64,6 @@ def _arith(groups, per):
     assert len(seen) == groups * per
     surplus = (-(-groups // 8) * 8 - groups) * per
     return {"arith: surplus workgroups leave (grp >= nshare)" if surplus else "arith: every workgroup has an item"}
-
-
-def _shares(B, H, nwin, grid):
-    """per workgroup of wattn_p_kernel: (x, sx, nwg_x, windows of the XCD, it0, it1)."""
-    ngrp = B * nwin
-    for wg in range(grid):
-        x, sx = wg & 7, wg >> 3
-        nwg_x = (grid + 7 - x) >> 3
-        nwin_x = (ngrp + 7 - x) >> 3
-        cnt_x = nwin_x * H
-        yield wg, x, sx, nwg_x, nwin_x, sx * cnt_x // nwg_x, (sx + 1) * cnt_x // nwg_x
 
 
 def _walk_branches(lists, B, H, nwin, grid, cus, name):
@@ -116,38 +108,24 @@ def _wattn_p_lists(B, H, nwin, cus):
 
 
 def _wattn_asm_lists(B, H, cus):
-    """wattn_worklist of psam_wattn_asm_80 (the 64 x 64 map: 25 windows)."""
+    """wattn_work_list of psam_wattn_asm_80 (the 64 x 64 map: 25 windows)."""
     nwin = NWIN64
     grid = min(B * nwin * H, cus)
-    lists, out = [], set()
-    for wg, x, sx, nwg_x, nwin_x, it0, it1 in _shares(B, H, nwin, grid):
-        if nwg_x % H == 0:
-            lanes, hh, lane = nwg_x // H, sx % H, sx // H
-            l = [(q, hh) for q in range(lane, nwin_x, lanes)]
+    lists, one_head = A.wattn_asm_lists(B, H, grid)
+    out = set()
+    for f in one_head:
+        if f:
             out.add("wattn_asm: nwg_x % H == 0 (one head per workgroup)" + (", grid == CUs" if grid == cus else ", grid < CUs"))
         else:
-            l = [divmod(i, H) for i in range(it0, it1)]
             out.add("wattn_asm: nwg_x % H != 0 (contiguous shares)")
-        lists.append([((q * 8 + x) // nwin, h, (q * 8 + x) % nwin) for q, h in l])
     return out | _walk_branches(lists, B, H, nwin, grid, cus, "wattn_asm")
 
 
 def _gattn_asm_table(B, H, nqb):
-    """gattn_worklist and the kernel's decode of its entries; every (b, h, query block) exactly once."""
+    """gattn_work_table and the kernel's decode of its entries; every (b, h, query block) exactly once."""
     items = B * H * nqb
-    per = -(-items // XCDS)
-    tab = [-1] * (per * XCDS)
-    for x in range(XCDS):
-        i0, i1 = items * x // XCDS, items * (x + 1) // XCDS
-        for i in range(i0, i1):
-            tab[(i - i0) * XCDS + x] = ((i // nqb) << 10) | (i % nqb)
-    M = (65536 + H - 1) // H
-    seen = set()
-    for e in tab:
-        if e >= 0:
-            grp, qb = e >> 10, e & 0x3ff
-            b = (grp * M) >> 16
-            seen.add((b, grp - b * H, qb))
+    tab = A.gattn_asm_table(B * H, nqb, XCDS)
+    seen = set(A.gattn_asm_decode(tab, H))
     assert seen == {(b, h, q) for b in range(B) for h in range(H) for q in range(nqb)}, "the table or its decode loses an item"
     out = {"gattn_asm: padded table (-1 entries)" if -1 in tab else "gattn_asm: no padding"}
     if items < XCDS:
