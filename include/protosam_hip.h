@@ -79,8 +79,9 @@ int psam_gemm_set_tile(int tile);
  * (0 before the first call): what tests and A/B tools check a forced tile against. 12 (four-deep ring) and 13 (64x64) are reported
  * whenever those kernels ran, forced or chosen for a small launch; a forced 12 / 13 that cannot take the call reports 1. */
 int psam_gemm_last_tile(int* tile);
-/* Schedule variant of the assembly GEMM (tile 15): 0 = the shipped kernels; n > 0 selects the numbered experiment kernels of a
- * library built with `make GENFLAGS=--experiments` (csrc/gemm_asm_gen.py; a missing variant makes the next GEMM return an error). */
+/* Variant of the assembly GEMM (tiles 15 / 16 / 17): 0 = the shipped kernels; 1 = their traced forms, which count cycles per K-tile
+ * loop and per epilogue (read back with PSAM_GEMM_ASM_TRACE set) and exist only in a library built with `make GENFLAGS=--trace`
+ * (csrc/gemm_asm_gen.py). Any value whose kernels the library does not hold makes the next GEMM return an error. */
 int psam_gemm_asm_variant(int variant);
 /* Dispatch switches of psam_gemm_f16 (1 = on, the default; initial values also from the environment): "asm" (PSAM_GEMM_ASM) the
  * assembly kernels for the large tiles, "half_tiles" (PSAM_GEMM_HALF) the half-tile assembly kernels for shapes with few 256x256

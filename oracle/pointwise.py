@@ -1,5 +1,5 @@
 """Oracle of the two pointwise functions every transformer block runs: the GELU of the GEMM epilogues (EPI_GELU_F16: common.h gelu_erf,
-csrc/gemm_asm_gen.py gelu_quad / gelu_pair, csrc/gemm_asm2_gen.py gelu_scalar) and the row LayerNorm psam_layernorm (csrc/layernorm.hip).
+csrc/gemm_asm_gen.py gelu_quad, csrc/gemm_asm2_gen.py gelu_scalar) and the row LayerNorm psam_layernorm (csrc/layernorm.hip).
 CPU torch / numpy only. Used by tests/test_pointwise_reference_cpu.py (no GPU: the references alone pass, every injected fault fails) and
 by tests/test_gelu_epilogue_gpu.py / tests/test_layernorm_gpu.py (the kernels, through the same checks).
 
@@ -28,9 +28,10 @@ interleaved row by row. offset_c: the bound's variance term grows as D u c / std
 std^2, so the fault shows only where c is large against D: 1000 up to D = 256, 4000 beyond, where u c^2 reaches the variance itself (the
 CPU test asserts both sides at every D)."""
 import functools
+import importlib
 import math
 import os
-import re
+import sys
 from dataclasses import dataclass
 
 import numpy as np
@@ -156,15 +157,17 @@ def gelu_check(y, x64, what):
 
 
 def sigpoly_constants():
-    """(c4, c3, c2, c1, c0) of gelu_quad as fp32 bit patterns read out of csrc/gemm_asm_gen.py: the SGPR list [c4 c4 c2 c2 c1 c1 c0 c0] and the
-    VGPR constant c3 of the `sigpoly` branch"""
-    src = open(os.path.join(ROOT, "protosam_amd", "csrc", "gemm_asm_gen.py")).read()
-    blk = src[src.index('GELU_MODE) == "sigpoly":'):]
-    blk = blk[:blk.index("elif self.epi == EPI_GELU_F16")]
-    lst = [int(v, 16) for v in re.findall(r"0x[0-9a-fA-F]{8}", re.search(r"consts = \[(.*?)\]", blk, re.S).group(1))]
-    c3 = {int(v, 16) for v in re.findall(r"v_mov_b32 v%d, (0x[0-9a-fA-F]{8})", blk)}
-    assert len(lst) == 8 and lst[0::2] == lst[1::2] and len(c3) == 1, (lst, c3)
-    bits = np.array([lst[0], c3.pop(), lst[2], lst[4], lst[6]], dtype=np.uint32)
+    """(c4, c3, c2, c1, c0) of gelu_quad as fp32, from the names csrc/gemm_asm_gen.py emits them under: GELU_SGPR_CONSTS, the SGPR list
+    [c4 c4 c2 c2 c1 c1 c0 c0], and GELU_C3, the constant of the two VGPRs"""
+    csrc = os.path.join(ROOT, "protosam_amd", "csrc")
+    sys.path.insert(0, csrc)                       # (the generator imports its neighbour asm_common by name)
+    try:
+        gen = importlib.import_module("gemm_asm_gen")
+    finally:
+        sys.path.remove(csrc)
+    lst = list(gen.GELU_SGPR_CONSTS)
+    assert len(lst) == 8 and lst[0::2] == lst[1::2], lst
+    bits = np.array([lst[0], gen.GELU_C3, lst[2], lst[4], lst[6]], dtype=np.uint32)
     return bits.view(np.float32)
 
 

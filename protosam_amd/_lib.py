@@ -26,7 +26,7 @@ SIGNATURES = {
                                 c_void_p],
     "psam_gemm_set_tile": [c_int],
     "psam_gemm_last_tile": [ctypes.POINTER(c_int)],
-    "psam_gemm_asm_variant": [c_int],
+    "psam_gemm_asm_variant": [c_int],                 # 0 shipped kernels, 1 traced forms (make GENFLAGS=--trace)
     "psam_gemm_set_option": [ctypes.c_char_p, c_int],
     "psam_gemm_set_workspace": [c_void_p, c_size_t],
     "psam_layernorm": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float,

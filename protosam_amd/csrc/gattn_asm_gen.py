@@ -86,28 +86,21 @@ A_O, A_LT, A_Q, A_ONES = 0, 80, 96, 144      # O^T [d][qt] 4 each; l [qt] 4; Q f
 A_KF, A_VF, RING = 148, 172, 6               # rings of six K / V fragments (LDS reads land in AGPRs, the MFMAs take them from there)
 
 
-import os
-
 from asm_common import AsmWriter, LdsCounter, kernel_begin, kernel_end, kernel_metadata, module_text
 
 PER2 = 3             # side instructions per MFMA in phase 2 (4: no change)
-ABL = os.environ.get("PSAM_GEN_GATTN_ABLATE", "")      # experiments (results wrong): noexp, nosoft1, nosoft2, nomfma, norw
 # The running maximum only has to keep exp2(score - offset) inside fp16 / fp32 range, not to be the exact row maximum: every lane
 # compares its OWN 16 scores of a query against the running offset + 8, and only when some lane trips does the out-of-line rescale
 # reduce the maxima across the four lanes that share the query (two lane swaps per query tile). The common iteration then carries
-# no cross-lane traffic at all: 32 instructions fewer per tile and wave, 3727 -> 3650 cycles (0 = the round-3 form, swaps in every
-# iteration). (Tried with it: K pieces 8 / 9 to waves 0 / 1 and V pieces 8 / 9 to waves 2 / 3, five real DMA pieces per wave
-# instead of six / four - no change, 3760 vs 3745 cycles: the barrier's cost is not the waves' DMA imbalance.)
-LAZYMAX = os.environ.get("PSAM_GEN_GATTN_LAZYMAX", "1") != "0"
-RH_AT = os.environ.get("PSAM_GEN_GATTN_RH_AT", "phase2")        # fused: where the rel_h MFMAs of the next tile go ("phase1": the first form)
-DMA_AT = os.environ.get("PSAM_GEN_GATTN_DMA_AT", "auto")        # "phase1" / "decision" / "auto" (see iteration())
-# key blocks tt (of the four 16-key blocks of a tile) whose exp2 / packing is DEFERRED to phase 1 of the next iteration (experiment, off):
-# phase 2 carries 160 softmax instructions on 48-60 MFMAs, phase 1 some 50 on 48, and the P V MFMAs of the tile's second key half (the
-# only readers of block 3's probabilities) run in the second half of that phase 1 - by a per-phase max(VALU, MFMA) model worth 300 of
-# 3700 cycles. Measured (tools/r05/gattn_late.sh, 16-slice ViT-H layer, fused / rel): none 1962-1971 / 1905-1916 us, "3" 1973-1988 /
-# 1882-1889, "2,3" 1963-1974 / 1870-1872, "2" 1970-1998 / 1875-1902 - nothing beyond the run-to-run spread: the loop is not bound by the
-# balance of its phases but by the instruction issue of its one wave per SIMD ("What comes next").
-LATE_TT = tuple(int(v) for v in os.environ.get("PSAM_GEN_GATTN_LATE", "").split(",") if v != "")
+# no cross-lane traffic at all: 32 instructions fewer per tile and wave than with the swaps in every iteration, 3727 -> 3650 cycles.
+# (Tried with it: K pieces 8 / 9 to waves 0 / 1 and V pieces 8 / 9 to waves 2 / 3, five real DMA pieces per wave instead of six /
+# four - no change, 3760 vs 3745 cycles: the barrier's cost is not the waves' DMA imbalance.)
+# Also measured and dropped: the exp2 / packing of one or two of a tile's four 16-key blocks deferred to phase 1 of the next
+# iteration. Phase 2 carries 160 softmax instructions on 48-60 MFMAs, phase 1 some 50 on 48, and the P V MFMAs of the tile's second key
+# half (the only readers of block 3's probabilities) run in the second half of that phase 1 - by a per-phase max(VALU, MFMA) model worth
+# 300 of 3700 cycles. 16-slice ViT-H layer, fused / rel: none 1962-1971 / 1905-1916 us, block 3 1973-1988 / 1882-1889, blocks 2 and 3
+# 1963-1974 / 1870-1872, block 2 1970-1998 / 1875-1902 - nothing beyond the run-to-run spread: the loop is not bound by the balance of
+# its phases but by the instruction issue of its one wave per SIMD ("What comes next").
 
 
 class GenA(AsmWriter):
@@ -135,16 +128,10 @@ class GenA(AsmWriter):
         lds = LdsCounter(e)
 
         def need(keys):
-            if not keys or "noreads" in ABL:
-                return
-            lds.need(max(issued[k] for k in keys))
+            if keys:
+                lds.need(max(issued[k] for k in keys))
 
         def emit(op):
-            if "nodeps" in ABL and op[0] == "v" and not op[1].startswith("v_mfma"):     # every VALU filler an independent move
-                e("v_mov_b32 v%d, v%d" % (V_T + (lds.n + len(self.L)) % 7, V_LI))
-                return
-            if "noreads" in ABL and op[0] == "ds":
-                return
             if op[0] == "ds":
                 issued[op[2]] = lds.issue(op[1])
             elif op[0] == "v":
@@ -153,19 +140,10 @@ class GenA(AsmWriter):
             else:
                 e(op[1])
 
-        if "noreads" in ABL:
-            pre, mfmas = [], [(t, [], []) for (t, d, pn) in mfmas]
         for op in pre:
             emit(op)
         fi = 0
         for (txt, deps, pinned) in mfmas:
-            nf = [d[1] for d in deps if d[0] == "nf"]       # ("nf", n): the first n fillers are emitted before this MFMA (it reads what they write)
-            if nf and fi < min(max(nf), len(fillers)):
-                while fi < min(max(nf), len(fillers)):
-                    emit(fillers[fi])
-                    fi += 1
-                e("s_nop 1")
-            deps = [d for d in deps if d[0] != "nf"]
             need(deps)
             e(txt)
             for op in pinned:
@@ -197,7 +175,7 @@ class GenA(AsmWriter):
         r = A_KF + 4 * (k % RING)
         return [("ds", "ds_read_b128 a[%d:%d], v%d offset:%d" % (r, r + 3, V_KA + s, K_BASE + tt * 16 * RLD), ("kf", k))]
 
-    def pv_mfmas(self, vbuf, late_nf=0):
+    def pv_mfmas(self, vbuf):
         """row sums and O^T += V^T P^T of the tile whose P sits in V_P; fragment k is read right behind the last MFMA of fragment
         k - 2 (its ring slot was fragment k - 3's), the first two up front"""
         AH = RING - 2          # fragments in flight ahead of the one being consumed
@@ -206,13 +184,10 @@ class GenA(AsmWriter):
             pre += self.v_read(k, vbuf)
         M = []
         for s2 in range(2):
-            first = len(M)
             for qt in range(4):
                 p = V_P + (qt * 2 + s2) * 4
                 M.append(["v_mfma_f32_16x16x32_f16 a[%d:%d], a[%d:%d], v[%d:%d], a[%d:%d]" % (
                     A_LT + 4 * qt, A_LT + 4 * qt + 3, A_ONES, A_ONES + 3, p, p + 3, A_LT + 4 * qt, A_LT + 4 * qt + 3), [], []])
-            if late_nf and any((tt >> 1) == s2 for tt in LATE_TT):
-                M[first][1] = M[first][1] + [("nf", late_nf)]       # this half of P is completed by the first late_nf fillers of the phase
             for d in range(self.DB):
                 k = s2 * self.DB + d
                 r = A_VF + 4 * (k % RING)
@@ -254,14 +229,12 @@ class GenA(AsmWriter):
                 F.append(("ds", "ds_read_b128 v[%d:%d], v%d offset:%d" % (d0, d0 + 3, V_RW + tt, qt * 4096), ("rw", tt * 4 + qt)))
         return F
 
-    def soft1(self, st, with_rw):
+    def soft1(self, st):
         """the row maxima of score set `st` (raw scores + rel_w / scale; times scale log2 e, + rel_h): the VALU stream of phase 1"""
-        F = self.rw_reads(st ^ 1) if with_rw else []
-        # in-lane maxima of the 16 values of every query tile (two independent v_max3 chains each), then - all four tiles side by
-        # side, so that no instruction waits for the one before it - the two lane swaps (xor 16, xor 32) and scale / rel_h
+        F = []
+        # in-lane maxima of the 16 values of every query tile (two independent v_max3 chains each), then scale / rel_h (the maxima
+        # across the lanes that share a query: rescale_routine, only when a lane trips)
         t = [V_MXT + i for i in range(4)]
-        xs = [V_T + i for i in range(4)]          # v18..21 / v22..24 + v29: free outside the decision / rescale code
-        ys = [V_T + 4, V_T + 5, V_T + 6, V_MXT + 4]
         for qt in range(4):
             vals = [self.s_idx(st, tt, qt) + j for tt in range(4) for j in range(4)]
             m = V_MX + qt
@@ -271,24 +244,14 @@ class GenA(AsmWriter):
             F.append(("v", "v_max3_f32 v%d, v%d, v%d, v%d" % (m, m, t[0], t[1]), []))
             F.append(("v", "v_max3_f32 v%d, v%d, v%d, v%d" % (t[2], t[2], t[3], vals[15]), []))
             F.append(("v", "v_max_f32 v%d, v%d, v%d" % (m, m, t[2]), []))
-        for swap in (() if LAZYMAX else ("v_permlane16_swap_b32", "v_permlane32_swap_b32")):
-            for qt in range(4):
-                F.append(("v", "v_mov_b32 v%d, v%d" % (xs[qt], V_MX + qt), []))
-            for qt in range(4):
-                F.append(("v", "v_mov_b32 v%d, v%d" % (ys[qt], V_MX + qt), []))
-            for qt in range(4):
-                F.append(("v", "%s v%d, v%d" % (swap, xs[qt], ys[qt]), []))
-            for qt in range(4):
-                F.append(("v", "v_max_f32 v%d, v%d, v%d" % (V_MX + qt, xs[qt], ys[qt]), []))
         for qt in range(4):
             F.append(("v", "v_fma_f32 v%d, v%d, s%d, v%d" % (V_MX + qt, V_MX + qt, S_SL2, V_BH + qt), []))   # * scale log2(e) + rel_h of this row of keys
         return F
 
-    def soft2(self, st, tts=(0, 1, 2, 3)):
-        """exp2 and fp16 packing of the key blocks `tts` of score set `st` into P: the VALU stream of phase 2 (and, for the deferred
-        blocks, the head of the next iteration's phase 1)"""
+    def soft2(self, st):
+        """exp2 and fp16 packing of the four key blocks of score set `st` into P: the VALU stream of phase 2"""
         F = []
-        for tt in tts:
+        for tt in range(4):
             for qt in range(4):
                 s0 = self.s_idx(st, tt, qt)
                 for j in range(4):
@@ -323,19 +286,19 @@ class GenA(AsmWriter):
         self.lab("L_resc_%s" % tag)
         e("s_nop 7")
         e("s_nop 7")
-        if LAZYMAX:      # the lanes' own maxima -> the maxima of the query rows (the four lanes li, li + 16, li + 32, li + 48 share a query)
-            xs = [V_T + i for i in range(4)]
-            ys = [V_T + 4, V_T + 5, V_T + 6, V_MXT + 4]
-            for swap in ("v_permlane16_swap_b32", "v_permlane32_swap_b32"):
-                for qt in range(4):
-                    e("v_mov_b32 v%d, v%d" % (xs[qt], V_MX + qt))
-                    e("v_mov_b32 v%d, v%d" % (ys[qt], V_MX + qt))
-                e("s_nop 1")
-                for qt in range(4):
-                    e("%s v%d, v%d" % (swap, xs[qt], ys[qt]))
-                e("s_nop 1")
-                for qt in range(4):
-                    e("v_max_f32 v%d, v%d, v%d" % (V_MX + qt, xs[qt], ys[qt]))
+        # the lanes' own maxima -> the maxima of the query rows (the four lanes li, li + 16, li + 32, li + 48 share a query)
+        xs = [V_T + i for i in range(4)]          # v18..21 / v22..24 + v29: free outside the decision / rescale code
+        ys = [V_T + 4, V_T + 5, V_T + 6, V_MXT + 4]
+        for swap in ("v_permlane16_swap_b32", "v_permlane32_swap_b32"):
+            for qt in range(4):
+                e("v_mov_b32 v%d, v%d" % (xs[qt], V_MX + qt))
+                e("v_mov_b32 v%d, v%d" % (ys[qt], V_MX + qt))
+            e("s_nop 1")
+            for qt in range(4):
+                e("%s v%d, v%d" % (swap, xs[qt], ys[qt]))
+            e("s_nop 1")
+            for qt in range(4):
+                e("v_max_f32 v%d, v%d, v%d" % (V_MX + qt, xs[qt], ys[qt]))
         for qt in range(4):
             e("v_max_f32 v%d, v%d, v%d" % (V_T + 4, V_MRUN + qt, V_MX + qt))
             e("v_sub_f32 v%d, v%d, v%d" % (V_T + 5, V_MRUN + qt, V_T + 4))
@@ -521,11 +484,10 @@ class GenA(AsmWriter):
                 ops.append(("s", "buffer_load_dwordx4 v%d, s[%d:%d], 0 offen lds" % (vo + i, srd, srd + 3)))
                 if i == 2:
                     ops.append(("s", "s_mov_b64 exec, -1"))
-            if "dma0" not in ABL:
-                ops.append(("s", "s_add_u32 s%d, s%d, s%d" % (srd, srd, S_KSTEP)))
-                ops.append(("s", "s_addc_u32 s%d, s%d, 0" % (srd + 1, srd + 1)))
-                ops.append(("s", "s_max_u32 s%d, s%d, s%d" % (srd + 2, srd + 2, S_KSTEP)))
-                ops.append(("s", "s_sub_u32 s%d, s%d, s%d" % (srd + 2, srd + 2, S_KSTEP)))
+            ops.append(("s", "s_add_u32 s%d, s%d, s%d" % (srd, srd, S_KSTEP)))
+            ops.append(("s", "s_addc_u32 s%d, s%d, 0" % (srd + 1, srd + 1)))
+            ops.append(("s", "s_max_u32 s%d, s%d, s%d" % (srd + 2, srd + 2, S_KSTEP)))
+            ops.append(("s", "s_sub_u32 s%d, s%d, s%d" % (srd + 2, srd + 2, S_KSTEP)))
         return ops
 
     def dma(self):
@@ -550,20 +512,16 @@ class GenA(AsmWriter):
             e("s_add_u32 s%d, s%d, s%d" % (S_T0, S_RHT, S_QT + qt - 1))
             e("buffer_load_dword v%d, v%d, s[%d:%d], s%d offen" % (V_BHN + qt, V_RHO, SRD_RH, SRD_RH + 3, S_T0))
 
-    def iteration(self, par, has_pv, has_qk, tag, dma_first=True):
+    def iteration(self, par, has_pv, has_qk, tag):
         """tile i with i & 1 == par: scores in set `par`, P V of tile i-1 from V buffer (i-1) & 1 = par ^ 1, scores of tile i+1 from
-        K buffer par ^ 1 into set par ^ 1. The iteration opens with the DMA of K(i+2) / V(i) into the buffers the previous iteration's
-        barrier released (woven into phase 1 like everything else that is not an MFMA)."""
+        K buffer par ^ 1 into set par ^ 1. The DMA of K(i+2) / V(i) goes into the buffers the previous iteration's barrier released."""
         e = self.e
         self.buffers()
         if self.mode == "rel":
             self.bh_loads()
         if self.mode == "norel" and not has_qk:
             self.mask_last_tile(par, tag)
-        late = self.soft2(par ^ 1, LATE_TT) if (has_pv and LATE_TT and "nosoft2" not in ABL) else []     # the previous tile's deferred blocks
-        if "noexp" in ABL:
-            late = [(op[0], op[1].replace("v_exp_f32", "v_mov_b32"), op[2]) if op[0] == "v" else op for op in late]
-        F = self.soft1(par, False)
+        F = self.soft1(par)
         if has_qk and self.mode != "norel":   # rel_w / scale of the next tile: one read per five other operations (needed in phase 2 only)
             rw = self.rw_reads(par ^ 1)
             out, k = [], 0
@@ -573,56 +531,34 @@ class GenA(AsmWriter):
                     k += 1
                 out.append(op)
             F = out + rw[k:]
-        if "nosoft1" in ABL:
-            F = []
-        nrh = 0
-        rh_phase1 = RH_AT == "phase1"
-        rh_pending = None
-        if self.mode == "fused" and has_qk and rh_phase1:   # (first form: rel_h of tile i + 1 ahead of the P V MFMAs - 4600 cycles per tile
-            RM = self.rh_mfmas()                            #  against 3690 of the _rel kernel in the back-to-back benchmark: kept for A/B)
-            RM[-1] = (RM[-1][0], [], self.rh_loads())
-            rh_pending = RM
-            nrh = 3 * len(RM)
         # the six DMA pieces of an iteration: woven into phase 1 behind its first MFMAs (no-bias kernel), or issued back to back in the
         # MFMA-free stretch between the phases (rel-pos kernels: 1951 -> 1909 us per 16-slice ViT-H call, 1227 -> 1195 ViT-B; the no-bias
         # kernel runs 4 % slower that way: its phase 1 has no rel_w reads to share the slots with)
-        dma_late = (DMA_AT == "decision") if DMA_AT != "auto" else self.mode != "norel"
-        head = F[:nrh] + (self.dma_ops() if (dma_first and "nodma" not in ABL and not dma_late) else [])
-        # the deferred blocks first (the rel_w reads of the next tile overwrite their score registers: those come behind, in program
-        # order), and the P V MFMAs of the key half they complete wait for them
-        F = head + late + F[nrh:]
-        pre, M = self.pv_mfmas(par ^ 1, len(head) + len(late) if late else 0) if has_pv else ([], [])
-        if "nomfma" in ABL:
-            pre, M = [], []
-        if rh_pending is not None and "nomfma" not in ABL:
-            M = rh_pending + M
+        dma_late = self.mode != "norel"
+        if not dma_late:
+            F = self.dma_ops() + F
+        pre, M = self.pv_mfmas(par ^ 1) if has_pv else ([], [])
         self.merge(pre, M, F, 3)
-        if dma_first and "nodma" not in ABL and dma_late:     # (experiment: the pieces in the MFMA-free stretch between the phases)
+        if dma_late:
             self.dma()
         self.decision(tag)
         pre, M = self.qk_mfmas(par ^ 1, par ^ 1) if has_qk else ([], [])
-        rh_late = self.mode == "fused" and has_qk and not rh_phase1
-        if rh_late and "nomfma" not in ABL:
+        rh = self.mode == "fused" and has_qk
+        if rh:
             # rel_h of tile i + 1 BEHIND the score MFMAs of phase 2 - the phase that carries 160 softmax instructions on 48 MFMAs gets
-            # twelve more to hide them behind. Its table row was requested an iteration ago, behind the six DMA pieces of that iteration:
-            # everything but this iteration's own six pieces has landed at vmcnt(6); the row of tile i + 2 is requested behind the last of
-            # these MFMAs (they have read the old one), so the closing wait leaves 6 + KS requests in flight.
+            # twelve more to hide them behind (ahead of the P V MFMAs of phase 1, the first form: 4600 cycles per tile against 3690 of
+            # the _rel kernel in the back-to-back benchmark). Its table row was requested an iteration ago, behind the six DMA pieces of
+            # that iteration: everything but this iteration's own six pieces has landed at vmcnt(6); the row of tile i + 2 is requested
+            # behind the last of these MFMAs (they have read the old one), so the closing wait leaves 6 + KS requests in flight.
             RM = self.rh_mfmas()
             M[-1] = (M[-1][0], M[-1][1], list(M[-1][2]) + [("s", "s_waitcnt vmcnt(6)")])
             RM[-1] = (RM[-1][0], [], self.rh_loads())
             M = M + RM
-        F = self.soft2(par, tuple(tt for tt in range(4) if not (has_qk and tt in LATE_TT)))     # (the last tile has no next phase 1)
-        if "noexp" in ABL:
-            F = [(op[0], op[1].replace("v_exp_f32", "v_mov_b32"), op[2]) if op[0] == "v" else op for op in F]
-        if "nosoft2" in ABL:
-            F = []
-        if "nomfma" in ABL:
-            pre, M = [], []
+        F = self.soft2(par)
         self.merge(pre, M, F, max(PER2, -(-len(F) // max(len(M), 1))))      # (hd = 64: 32 score MFMAs carry the same 160 instructions)
-        if "nowait" not in ABL:
-            # K(i+2), V(i) (requested an iteration ago) and rel_h of the next tile have landed; the six pieces this iteration
-            # requested (every wave issues six, see dma_ops) may stay in flight
-            e("s_waitcnt vmcnt(%d)" % (0 if "nodma" in ABL else 6 + (self.KS if rh_late else 0)))
+        # K(i+2), V(i) (requested an iteration ago) and rel_h of the next tile have landed; the six pieces this iteration
+        # requested (every wave issues six, see dma_ops) may stay in flight
+        e("s_waitcnt vmcnt(%d)" % (6 + (self.KS if rh else 0)))
         e("s_mov_b32 s%d, s%d" % (S_T0, S_R0))
         e("s_mov_b32 s%d, s%d" % (S_R0, S_R1))
         e("s_mov_b32 s%d, s%d" % (S_R1, S_R2))
@@ -630,12 +566,10 @@ class GenA(AsmWriter):
         if self.mode == "rel":
             for qt in range(4):
                 e("v_mul_f32 v%d, 0x%08x, v%d" % (V_BH + qt, 0x3fb8aa3b, V_BHN + qt))     # * log2(e)
-        elif self.mode == "fused" and has_qk:
-            if rh_late:
-                e("s_nop 7")      # (the last rel_h MFMA is ~15 instructions old: its accumulator read below stays clear of the XDL write hazard)
+        elif rh:
+            e("s_nop 7")          # (the last rel_h MFMA is ~15 instructions old: its accumulator read below stays clear of the XDL write hazard)
             self.rh_finish()
-        if "nobar" not in ABL:
-            e("s_barrier")
+        e("s_barrier")
 
     # ------------------------------------------------------------------ kernel
     def kernel(self):

@@ -1219,7 +1219,7 @@ extern "C" const unsigned char psam_gemm_asm_co_end[];
 struct AsmGemmArgs {
   const void* A; const void* W; const void* bias; void* out; const void* resid; const void* gamma; const void* tab;
   int M, N, K, lda, ldw, ldo, ldr, G, flags, pad;
-  void* trace;   // experiment variants only (gemm_asm_gen.py --experiments): uint4 per workgroup {k-loop cycles, epilogue cycles, K-tiles, 0}
+  void* trace;   // traced forms only (gemm_asm_gen.py --trace): uint4 per workgroup {k-loop cycles, epilogue cycles, K-tiles, 0}
   // folded-LayerNorm producer (psam_gemm_asm_f32_ln only; the other kernels' kernarg segment ends at 104)
   void* out16; float* stats; int ld16, pad2;
 };
@@ -1227,7 +1227,7 @@ static_assert(sizeof(AsmGemmArgs) == 128, "kernarg layout of gemm_asm_gen.py");
 // The code object is loaded once per DEVICE (a hipModule_t / hipFunction_t belongs to the device that was current at load time).
 struct AsmModule { hipModule_t mod = nullptr; int state = 0; std::map<int, std::vector<hipFunction_t>> fns; std::map<std::string, hipFunction_t> named; };
 static std::map<int, AsmModule> g_asm;   // device -> module; fns: family * 1000 + variant -> {f16, gelu, f32, ...}; state 0 not tried, 1 loaded, -1 failed
-static int g_asm_variant = 0;   // 0 = the shipped schedule; > 0: experiment builds (kernel names carry the suffix _v<n>)
+static int g_asm_variant = 0;   // 0 = the shipped kernels; 1 = their traced forms (kernel names carry the suffix _v1; built by GENFLAGS=--trace only)
 extern "C" int psam_gemm_asm_variant(int v) {
   g_asm_variant = v;
   return PSAM_OK;
@@ -1236,9 +1236,7 @@ static AsmModule* asm_module() {
   AsmModule& m = g_asm[psam_current_device()];
   if (m.state == 0) {
     m.state = -1;
-    const char* path = getenv("PSAM_GEMM_ASM_CO");          // (experiments: a code object built from another schedule)
-    hipError_t st = path ? hipModuleLoad(&m.mod, path) : hipModuleLoadData(&m.mod, psam_gemm_asm_co);
-    if (st != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+    if (hipModuleLoadData(&m.mod, psam_gemm_asm_co) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
     m.state = 1;
   }
   return m.state < 0 ? nullptr : &m;

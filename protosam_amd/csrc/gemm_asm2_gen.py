@@ -20,7 +20,7 @@ barrier whose counted wait they ride on). Price: a 256x128 tile re-reads the A p
   * the K-tile stream is continuous across half-tiles; the first half-tile of a workgroup runs a dummy epilogue with a
     zero-sized output descriptor, the last one is followed by a stand-alone drain of the same instruction stream.
 
-Run:  python3 gemm_asm2_gen.py > gemm_asm2.s
+Run:  python3 gemm_asm2_gen.py [--trace] > gemm_asm2.s
 """
 import sys
 
@@ -171,41 +171,28 @@ class GenP(AsmWriter):
 
     def base_slots(self):
         """the k-loop's own side instructions of one iteration: list per slot of Op"""
-        o = self.o
         slots = [[] for _ in range(32)]
         for i in range(12):
-            if not o.get("no_reads"):
-                slots[RD23[i]].append(Op("ds", self.frag_read(2 + i // 6, 2 + i // 6, i % 6)))
+            slots[RD23[i]].append(Op("ds", self.frag_read(2 + i // 6, 2 + i // 6, i % 6)))
         # SRD advance of the previous iteration's pieces (the prologue leaves it to iteration 0)
         for i, ins in enumerate(self.dma_advance()):
             slots[1 + i // 3].append(Op("salu", ins))
         for i, r in enumerate((V_FA + 2, V_FA + 3, V_FB + 2, V_FB + 3)):
             slots[8 + i // 2].append(Op("valu", "v_add_u32 v%d, s%d, v%d" % (r, S_D23, r)))
-        if not o.get("no_barrier"):
-            slots[BAR_A] += [Op("misc", "s_waitcnt lgkmcnt(0)"), Op("misc", "s_barrier")]
+        slots[BAR_A] += [Op("misc", "s_waitcnt lgkmcnt(0)"), Op("misc", "s_barrier")]
         slots[BAR_A] += [Op("salu", "s_cmp_eq_u32 s%d, 0" % S_DKREM), Op("misc", "SWITCH")]
         for p in range(12):
-            if o.get("no_dma"):
-                continue
             s = DMA_SLOTS[p]
             slots[s - 1].append(Op("salu", self.dma_m0(p)))
             slots[s].append(Op("dma", self.dma_issue(p)))
         issued = sum(1 for p in range(12) if DMA_SLOTS[p] <= BAR_B)
-        if not o.get("no_barrier"):
-            slots[BAR_B] += [Op("misc", "s_waitcnt vmcnt(%d)" % (0 if o.get("no_dma") else 12 + issued)), Op("misc", "s_barrier")]
+        slots[BAR_B] += [Op("misc", "s_waitcnt vmcnt(%d)" % (12 + issued)), Op("misc", "s_barrier")]
         for i in range(12):
-            if not o.get("no_reads"):
-                slots[RD01[i]].append(Op("ds", self.frag_read(i // 6, i // 6, i % 6)))
+            slots[RD01[i]].append(Op("ds", self.frag_read(i // 6, i // 6, i % 6)))
         for i, r in enumerate((V_FA, V_FA + 1, V_FB, V_FB + 1)):
             slots[31].append(Op("valu", "v_add_u32 v%d, s%d, v%d" % (r, S_D01, r)))
         for ins in self.rotate():
             slots[31].append(Op("salu", ins))
-        nf = 0
-        for s, k in sorted(o.get("fill", {}).items()):      # (experiments: k independent VALU fillers behind MFMA s)
-            for _ in range(k):
-                r = V_GT + nf % 16
-                nf += 1
-                slots[s].append(Op("valu", "v_fma_f32 v%d, v%d, v%d, v%d" % (r, r, V_GC, V_GC + 1)))
         return slots
 
     def emit_iter(self, par, slots, zero, drain=False):
@@ -321,9 +308,8 @@ class GenP(AsmWriter):
         Returns (list of iterations, each a list of 32 lists of Op)."""
         # VALU capacity behind MFMA s of an iteration (docs/history/tools/r04/exp12.sh: independent fillers in the k-loop: 4 per slot behind
         # MFMAs 8..31 cost nothing, 4 behind MFMAs 0..7 - the fragment reads and the descriptor advance - cost 52 cycles);
-        # a transcendental counts trans_w
-        caps = self.o.get("caps", [2] * 8 + [4] * 24)
-        trans_w = self.o.get("trans_w", 1.0)
+        # a transcendental counts like any other VALU instruction
+        caps = [2] * 8 + [4] * 24
         iters = []
 
         def slot(it, s):
@@ -332,19 +318,18 @@ class GenP(AsmWriter):
             return iters[it][s]
 
         # cursors: (iteration, slot)
-        state = {"v": (0, ST_WIN[0]), "vn": 0.0, "ds": (0, ST_WIN[0]), "st": (0, 0)}
+        state = {"v": (0, ST_WIN[0]), "vn": 0, "ds": (0, ST_WIN[0]), "st": (0, 0)}
 
         def place_valu(ops):
             it, s = state["v"]
             for op in ops:
-                w = trans_w if op.text.startswith(("v_exp_f32", "v_rcp_f32")) else 1.0
-                while state["vn"] + w > caps[s] + 1e-6:
+                while state["vn"] + 1 > caps[s]:
                     s += 1
-                    state["vn"] = 0.0
+                    state["vn"] = 0
                     if s == 32:
                         it, s = it + 1, 0
                 slot(it, s).append(op)
-                state["vn"] += w
+                state["vn"] += 1
             state["v"] = (it, s)
 
         def next_in(window, pos, strict=False):
@@ -363,7 +348,7 @@ class GenP(AsmWriter):
         # the epilogue starts behind barrier B of iteration 0 (bias went into the accumulators with the first MFMAs)
         for op in self.tile_setup_ops("prev"):
             slot(0, ST_WIN[0]).append(op)
-        state["vn"] = 99.0    # keep that slot for the set-up
+        state["vn"] = 99      # keep that slot for the set-up
 
         if self.epi != EPI_F32:
             gelu = self.epi == EPI_GELU_F16
@@ -382,8 +367,6 @@ class GenP(AsmWriter):
                         ops = [Op("valu", "v_accvgpr_read_b32 v%d, a%d" % (t + i, blk + i)) for i in range(4)]
                         if gelu:      # the four elements' chains interleaved: a dependent VALU pair issues 1.7x slower than an independent one
                             chains = [self.gelu_scalar(t + i, V_GT + 4 * i) for i in range(4)]
-                            if self.o.get("no_interleave"):
-                                chains = [sum(chains, [])]
                             for j in range(len(chains[0])):
                                 ops += [Op("valu", c[j]) for c in chains]
                         ops += [Op("valu", "v_cvt_pk_f16_f32 v%d, v%d, v%d" % (r, t, t + 1)), Op("valu", "v_cvt_pk_f16_f32 v%d, v%d, v%d" % (r + 1, t + 2, t + 3))]
@@ -449,19 +432,6 @@ class GenP(AsmWriter):
         for itl in iters:
             if any(op.kind == "ds" for s in DS_WIN for op in itl[s]):
                 itl[LGKM0].append(Op("misc", "s_waitcnt lgkmcnt(0)"))
-        abl = self.o.get("epi_ablate", ())            # (experiments: timing only, the results are wrong)
-        for itl in iters:
-            for s in range(32):
-                if "nolgkm" in abl:
-                    itl[s] = [op for op in itl[s] if not (op.text or "").startswith("s_waitcnt lgkmcnt(0)")]
-                if "nost" in abl:
-                    itl[s] = [op for op in itl[s] if op.kind != "st"]
-                if "nods" in abl:
-                    itl[s] = [op for op in itl[s] if op.kind != "ds"]
-                if "noacc" in abl:
-                    for op in itl[s]:
-                        if op.text and op.text.startswith("v_accvgpr_read_b32"):
-                            op.text = "v_mov_b32 %s v%d" % (op.text.split()[1], V_GC)
         return iters
 
     def merge(self, base, epi):
@@ -662,7 +632,7 @@ class GenP(AsmWriter):
         E = None
         for par in range(2):
             q = 1 - par
-            epi_iters = [] if self.o.get("no_epilogue") else self.schedule_epilogue(q)
+            epi_iters = self.schedule_epilogue(q)
             if E is None:
                 E = len(epi_iters)
             assert E == len(epi_iters)
@@ -670,8 +640,6 @@ class GenP(AsmWriter):
             # iteration 1), this half-tile's own epilogue operands (fp32), output descriptor switched on
             def make_el():
                 el = [[] for _ in range(32)]
-                if self.o.get("no_epilogue"):
-                    return el
                 el[0].append(Op("wait_vm", None, ("bias", 0)))
                 for k, op in enumerate(self.acc_init(q)):
                     el[k // 4].append(op)
@@ -688,7 +656,7 @@ class GenP(AsmWriter):
                 self.emit_iter(par, seq[1 + i], zero=False)
             self.emit_iter(par, seq[E + 1], zero=False)
             e("s_sub_u32 s%d, s%d, %d" % (S_KREM, S_NK, E + 1))
-            e("s_cmp_le_i32 s%d, 0" % S_KREM)               # (K < 64 (E + 1) is refused by the host; an experiment build must not hang on it)
+            e("s_cmp_le_i32 s%d, 0" % S_KREM)               # (K < 64 (E + 1) is refused by the host; a kernel must not hang on it)
             e("s_cbranch_scc1 L_half_done_%d_%s" % (par, n))
             self.L.append(".p2align 4")
             self.lab("L_loop_%d_%s" % (par, n))
@@ -708,17 +676,15 @@ class GenP(AsmWriter):
             e("s_cmp_eq_u32 s%d, -1" % S_TCUR)
             e("s_cbranch_scc0 L_half_%d_%s" % (1 - par, n))
             # ---- drain: the epilogue of THIS accumulator set, stand-alone (same instruction stream, no MFMAs)
-            if not self.o.get("no_epilogue"):
-                dr = self.schedule_epilogue(par)
-                for itl in dr:
-                    for s in range(32):
-                        for op in itl[s]:
-                            if op.kind == "wait_vm":
-                                e("s_waitcnt vmcnt(0)")
-                            else:
-                                e(op.text)
-                        if s == LGKM0:
-                            e("s_waitcnt lgkmcnt(0)")
+            for itl in self.schedule_epilogue(par):
+                for s in range(32):
+                    for op in itl[s]:
+                        if op.kind == "wait_vm":
+                            e("s_waitcnt vmcnt(0)")
+                        else:
+                            e(op.text)
+                    if s == LGKM0:
+                        e("s_waitcnt lgkmcnt(0)")
             e("s_branch L_exit_%s" % n)
         self.lab("L_exit_%s" % n)
         e("s_waitcnt vmcnt(0) lgkmcnt(0)")
@@ -758,38 +724,18 @@ class GenP(AsmWriter):
         return kernel_metadata(self.name, ["ptr"] * 7 + ["i32"] * 10 + ["ptr"], 163840, NUM_SGPR)
 
 
-def variants():
+def variants(trace=False):
+    """trace: also the `_v1` forms that count cycles per K-tile loop (gemm_asm_gen.variants)"""
     out = [("psam_gemm_asm2_f16", EPI_F16, {}), ("psam_gemm_asm2_gelu", EPI_GELU_F16, {}), ("psam_gemm_asm2_f32", EPI_F32, {})]
-    if "--experiments" in sys.argv:
-        ne = dict(trace=True, no_epilogue=True)
-        dma = sorted(set(DMA_SLOTS))
-        exps = [dict(trace=True), ne, dict(ne, no_dma=True)]
-        if "--fill" not in sys.argv:
-            exps += [dict(trace=True, caps=[3] * 8 + [4] * 24, trans_w=1.5), dict(trace=True, caps=[1] * 8 + [4] * 24),
-                     dict(trace=True, caps=[2] * 8 + [5] * 24, trans_w=2.0), dict(trace=True, caps=[3] * 8 + [5] * 24, trans_w=1.5), dict(trace=True, caps=[4] * 32),
-                     dict(trace=True, no_interleave=True), dict(trace=True, caps=[0] * 8 + [5] * 24, trans_w=1.5),
-                     dict(trace=True, epi_ablate=("nolgkm",)), dict(trace=True, epi_ablate=("nost",)), dict(trace=True, epi_ablate=("nods", "nolgkm")),     # v11..v13
-                     dict(trace=True, epi_ablate=("noacc",)), dict(trace=True, epi_ablate=("nods", "nolgkm", "nost")),                                   # v14, v15
-                     dict(trace=True, epi_ablate=("nods", "nolgkm", "nost", "noacc"))]                                                                  # v16
-            for i, o in enumerate(exps):
-                for nm, epi in (("f16", EPI_F16), ("gelu", EPI_GELU_F16), ("f32", EPI_F32)):
-                    out.append(("psam_gemm_asm2_%s_v%d" % (nm, i + 1), epi, o))
-            return out
-        exps += [dict(ne, fill={s: k for s in range(32)}) for k in (1, 2, 3, 4, 5)]                 # v4..v8: k fillers in every slot
-        exps += [dict(ne, fill={s: 4 for s in range(0, 8)}), dict(ne, fill={s: 4 for s in range(8, 22)}),      # v9..v11: by region
-                 dict(ne, fill={s: 4 for s in range(22, 32)}),
-                 dict(ne, fill={s: 4 for s in (11, 13, 15, 17, 19)}), dict(ne, fill={s: 4 for s in dma}),      # v12 / v13: quiet slots / DMA slots
-                 dict(ne, fill={s: 2 for s in dma}), dict(ne, fill={s: 6 for s in (11, 13, 15, 17, 19)})]      # v14 / v15
-        for i, o in enumerate(exps):
-            for nm, epi in (("f16", EPI_F16), ("gelu", EPI_GELU_F16), ("f32", EPI_F32)):
-                out.append(("psam_gemm_asm2_%s_v%d" % (nm, i + 1), epi, o))
+    if trace:
+        out += [(name + "_v1", epi, dict(trace=True)) for name, epi, _ in out]
     return out
 
 
-def build_all():
+def build_all(trace=False):
     """-> (assembly lines, metadata entries, {kernel name: E})"""
     lines, meta, es = [], [], {}
-    for name, epi, o in variants():
+    for name, epi, o in variants(trace):
         g = GenP(name, epi, o)
         g.kernel()
         lines += g.L
@@ -799,7 +745,7 @@ def build_all():
 
 
 def main():
-    lines, meta, es = build_all()
+    lines, meta, es = build_all("--trace" in sys.argv[1:])
     trailer = ["// %s: E = %d epilogue iterations (needs K >= %d)" % (k, v, 64 * (v + 1)) for k, v in es.items()]
     sys.stdout.write(module_text(lines, meta, trailer))
 

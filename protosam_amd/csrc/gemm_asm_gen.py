@@ -23,20 +23,17 @@ Structure (one persistent workgroup of FOUR waves per CU, one wave per SIMD, 512
     the workgroup's list of tiles (host-built table, XCD-aware order), the epilogue of a finished tile runs with the next
     tile's first two K-tiles already in flight.
 
-Run:  python3 gemm_asm_gen.py > gemm_asm.s
+Run:  python3 gemm_asm_gen.py [--trace] > gemm_asm.s      (--meta: the header csrc/gemm.hip includes instead)
 """
 import sys
 
 from asm_common import AsmWriter, kernel_begin, kernel_end, kernel_metadata, module_text, younger
 
-import os
-# cache policy of the operand DMA (experiment, round 5): "" default, " nt" streaming. PSAM_GEN_GEMM_DMA="a,w" e.g. ",nt": the W panels
-# (re-read by every row strip) streaming so that they do not displace the strip's A panel from the XCD's L2 between its two rounds
-_pol = (os.environ.get("PSAM_GEN_GEMM_DMA", ",") + ",").split(",")
-DMA_POLICY_A, DMA_POLICY_W = (" " + _pol[0] if _pol[0] else ""), (" " + _pol[1] if _pol[1] else "")
-# GELU of the fp16 epilogue: "sigpoly" (12 instructions per pair, within 3.4e-6 of gelu; gelu_quad) or "packed" (the A&S erf form, 18,
-# bit-identical to the HIP kernels' gelu_erf); PSAM_GEN_GELU overrides (A/B builds)
-GELU_MODE = os.environ.get("PSAM_GEN_GELU", "sigpoly")
+# GELU of the fp16 epilogue (gelu_quad): gelu(x) = x / (1 + exp2(x Q(x^2))), Q of degree 4. The bit patterns of -log2(e) Q's coefficients
+# as the kernel holds them: c4, c2, c1, c0 in the SGPR pairs s[S_C:S_C+7] (both halves of a packed operand), c3 in two VGPRs (an
+# instruction takes one SGPR operand). oracle/pointwise.py evaluates the same polynomial from these names.
+GELU_SGPR_CONSTS = [0xb658b1ce, 0xb658b1ce, 0x39bce2fa, 0x39bce2fa, 0xbdd78116, 0xbdd78116, 0xc01354b6, 0xc01354b6]
+GELU_C3 = 0x38b90ca2
 
 # ---------------------------------------------------------------- register map
 # SGPRs
@@ -54,7 +51,7 @@ S_FA, S_FB = 80, 81            # fragment half-tile bases of this wave
 S_LDA2, S_LDW2 = 82, 83
 S_T0, S_T1, S_T2, S_T3, S_T4 = 84, 85, 86, 87, 88
 S_ROW4, S_TOFF, S_N0X4, S_ROFF, S_RROW4 = 89, 90, 91, 92, 93
-S_C = 52            # s[52:64] GELU constants (pairs)
+S_C = 52            # s[52:59] GELU constants (pairs): GELU_SGPR_CONSTS
 S_ROW28, S_RROW28 = 65, 66
 S_ACC_LOOP, S_ACC_EPI, S_NKT = 67, 94, 95     # trace variants: cycles inside k-loops / epilogues, K-tiles done
 S_TS0, S_TS1, S_TRP = 96, 98, 100              # s_memtime stamps, trace pointer
@@ -108,7 +105,7 @@ class Gen(AsmWriter):
         assert not (self.sk and sched.get("trace"))
         # sched "mfma": "32x32x16" (4x4 blocks of 16 accumulators, 64 MFMA slots per K-tile) or "16x16x32" (8x8 blocks of 4, 128 slots)
         self.m16 = sched.get("mfma", "32x32x16") == "16x16x32"
-        assert not (self.m16 and (self.sk or sched.get("deep_ring") or sched.get("stagger")))
+        assert not (self.m16 and self.sk)
 
     # ------------------------------------------------------------ pieces of the program
     def item_rows_cols(self, item):
@@ -177,8 +174,8 @@ class Gen(AsmWriter):
 
     def dma_issue(self, p):
         if p < 8:
-            return "buffer_load_dwordx4 v%d, s[%d:%d], 0 offen%s lds" % (V_DA + p, SRD_A, SRD_A + 3, DMA_POLICY_A)
-        return "buffer_load_dwordx4 v%d, s[%d:%d], 0 offen%s lds" % (V_DB + p - 8, SRD_B, SRD_B + 3, DMA_POLICY_W)
+            return "buffer_load_dwordx4 v%d, s[%d:%d], 0 offen lds" % (V_DA + p, SRD_A, SRD_A + 3)
+        return "buffer_load_dwordx4 v%d, s[%d:%d], 0 offen lds" % (V_DB + p - 8, SRD_B, SRD_B + 3)
 
     def dma_advance(self):
         out = []
@@ -232,38 +229,32 @@ class Gen(AsmWriter):
             slots[s].append(ins)
         # fragment reads of k-step 1 of THIS tile during k-step 0
         for i, idx in enumerate(self.RD16_ORDER):
-            if not sc.get("no_reads"):
-                put(sc["rd1"][i], self.frag_read16(1, idx))
+            put(sc["rd1"][i], self.frag_read16(1, idx))
         for i, r in enumerate((self.M16_FA[1], self.M16_FB[1])):
             put(sc["tog1"][i], "v_xor_b32 v%d, 0x%x, v%d" % (r, LDS_BUF, r))
-        if not sc.get("no_epilogue") and not zero_copy:
+        if not zero_copy:
             put(sc["pre_slot"], "s_cmp_eq_u32 s%d, 1" % S_KREM)
             slots[sc["pre_slot"] + 1] += ["s_cbranch_scc1 L_pre_%s" % self.name, "L_pre_ret_%s:" % self.name]
         # barrier A: every wave has its fragments of this K-tile -> its buffer may be refilled
         a = sc["barA"]
-        if not sc.get("no_barrier"):
-            slots[a] += ["s_waitcnt lgkmcnt(0)", "s_barrier"]
+        slots[a] += ["s_waitcnt lgkmcnt(0)", "s_barrier"]
         put(a + 1, "s_cmp_eq_u32 s%d, 0" % S_DKREM)
         slots[a + 2] += ["s_cbranch_scc1 L_switch%s_%s" % (z, self.name), "L_switch_ret%s_%s:" % (z, self.name)]
         # DMA pieces of K-tile t+2
         for p in range(16):
             s = sc["dma"][p]
             assert p == 0 or s - sc["dma"][p - 1] >= 3
-            if sc.get("no_dma"):
-                continue
             put(s - 1, self.dma_m0(p))
             put(s, self.dma_issue(p))
         # barrier B: K-tile t+1 has landed
         b = sc["barB"]
         issued = sum(1 for p in range(16) if sc["dma"][p] <= b)
-        if not sc.get("no_barrier"):
-            assert not slots[b]
-            slots[b] += ["s_waitcnt vmcnt(%d)" % (0 if sc.get("no_dma") else issued), "s_barrier"]
+        assert not slots[b]
+        slots[b] += ["s_waitcnt vmcnt(%d)" % issued, "s_barrier"]
         # fragment reads of k-step 0 of the NEXT K-tile, then the DMA side's advance
         for i, idx in enumerate(self.RD16_ORDER):
             assert sc["rd0"][i] > b
-            if not sc.get("no_reads"):
-                put(sc["rd0"][i], self.frag_read16(0, idx))
+            put(sc["rd0"][i], self.frag_read16(0, idx))
         for i, ins in enumerate(self.dma_advance()):
             assert sc["adv"] + i > sc["dma"][15]
             put(sc["adv"] + i, ins)
@@ -296,26 +287,21 @@ class Gen(AsmWriter):
         slots = [[] for _ in range(64)]
         # fragment reads of k-steps 2 / 3 of THIS tile (sets S2, S3) during k-step 0
         for i in range(16):
-            if not sc.get("no_reads"):
-                slots[sc["rd23"][i]].append(self.frag_read(2 + i // 8, 2 + i // 8, i % 8))
+            slots[sc["rd23"][i]].append(self.frag_read(2 + i // 8, 2 + i // 8, i % 8))
         # toggles of the addresses used above (next use: next K-tile)
         for i, r in enumerate((V_FA + 2, V_FA + 3, V_FB + 2, V_FB + 3)):
             slots[sc["tog23"] + i].append("v_xor_b32 v%d, 0x%x, v%d" % (r, LDS_BUF, r))
         # the last K-tile of a tile requests the epilogue's operands (out of line)
-        if not sc.get("no_epilogue"):
-            slots[sc.get("pre_slot", 17)] += ["s_cmp_eq_u32 s%d, 1" % S_KREM, "s_cbranch_scc1 L_pre_%s" % self.name, "L_pre_ret_%s:" % self.name]
-        if self.lnc and not sc.get("no_epilogue"):
+        slots[sc.get("pre_slot", 17)] += ["s_cmp_eq_u32 s%d, 1" % S_KREM, "s_cbranch_scc1 L_pre_%s" % self.name, "L_pre_ret_%s:" % self.name]
+        if self.lnc:
             slots[48] += ["s_cmp_eq_u32 s%d, 1" % S_KREM, "s_cbranch_scc1 L_pre2_%s" % self.name, "L_pre2_ret_%s:" % self.name]
         # barrier A: every wave has its fragments of this K-tile -> its buffer may be refilled
         a = sc["barA"]
-        if not sc.get("no_barrier"):
-            slots[a] += ["s_waitcnt lgkmcnt(0)", "s_barrier"]
+        slots[a] += ["s_waitcnt lgkmcnt(0)", "s_barrier"]
         slots[a] += ["s_cmp_eq_u32 s%d, 0" % S_DKREM, "s_cbranch_scc1 L_switch_%s" % self.name, "L_switch_ret_%s:" % self.name]
         # DMA pieces of K-tile t+2
         for p in range(16):
             s = sc["dma"][p]
-            if sc.get("no_dma"):
-                continue
             slots[s - 1].append(self.dma_m0(p))
             slots[s].append(self.dma_issue(p))
         last = sc["dma"][15]
@@ -326,16 +312,12 @@ class Gen(AsmWriter):
         # barrier B: K-tile t+1 has landed
         b = sc["barB"]
         issued = sum(1 for p in range(16) if sc["dma"][p] <= b)
-        if not sc.get("no_barrier"):
-            slots[b] += ["s_waitcnt vmcnt(%d)" % (0 if sc.get("no_dma") else issued), "s_barrier"]
-        if sc.get("prio"):
-            slots[0].insert(0, "s_setprio %d" % sc["prio"])
+        slots[b] += ["s_waitcnt vmcnt(%d)" % issued, "s_barrier"]
         # fragment reads of k-steps 0 / 1 of the NEXT tile (sets S0, S1)
         for i in range(16):
             s = sc["rd01"][i]
             assert s > b
-            if not sc.get("no_reads"):
-                slots[s].append(self.frag_read(i // 8, i // 8, i % 8))
+            slots[s].append(self.frag_read(i // 8, i // 8, i % 8))
         return slots
 
     def ktile(self, slots, zero_first):
@@ -357,45 +339,13 @@ class Gen(AsmWriter):
                 return
 
     # ------------------------------------------------------------ epilogues
-    def gelu_pair(self, x, t):
-        """x: first of two consecutive VGPRs holding (acc + bias); t: first of 6 temporaries. The operation sequence of common.h
-        gelu_erf (A&S 7.1.26 on v_rcp / v_exp, 1 / sqrt(2) folded into the constants), two elements per packed instruction where
-        one exists: 18 instructions per pair. Bit-identical to the HIP kernels'."""
-        e = self.e
-        d, n, p = t, t + 2, t + 4
-        mode = self.sched.get("gelu_mode", "packed")
-        if mode == "none":
-            return
-        e("v_pk_mul_f32 v[%d:%d], v[%d:%d], v[%d:%d]" % (n, n + 1, x, x + 1, x, x + 1))                                        # x^2
-        for i in range(2):
-            e("v_fma_f32 v%d, |v%d|, s%d, 1.0" % (d + i, x + i, S_C))                                                          # 1 + p |x| / sqrt(2)
-        e("v_pk_mul_f32 v[%d:%d], v[%d:%d], s[%d:%d] op_sel_hi:[1,0]" % (n, n + 1, n, n + 1, S_C + 4, S_C + 5))               # * -log2(e) / 2
-        for i in range(2):
-            e(("v_mov_b32 v%d, v%d" if mode == "notrans" else "v_rcp_f32 v%d, v%d") % (d + i, d + i))
-        for i in range(2):
-            e(("v_mov_b32 v%d, v%d" if mode == "notrans" else "v_exp_f32 v%d, v%d") % (n + i, n + i))
-        e("v_pk_fma_f32 v[%d:%d], v[%d:%d], s[%d:%d], v[%d:%d] op_sel_hi:[1,0,1]" % (p, p + 1, d, d + 1, S_C + 2, S_C + 3, V_TMP + 8, V_TMP + 9))
-        for k in range(3):
-            e("v_pk_fma_f32 v[%d:%d], v[%d:%d], v[%d:%d], s[%d:%d] op_sel_hi:[1,1,0]" % (p, p + 1, p, p + 1, d, d + 1, S_C + 6 + 2 * k, S_C + 7 + 2 * k))
-        e("v_pk_mul_f32 v[%d:%d], v[%d:%d], v[%d:%d] neg_lo:[0,1] neg_hi:[0,1]" % (p, p + 1, d, d + 1, p, p + 1))             # t * -poly
-        e("v_pk_fma_f32 v[%d:%d], v[%d:%d], v[%d:%d], 1.0 op_sel_hi:[1,1,0]" % (p, p + 1, p, p + 1, n, n + 1))                # |erf|
-        for i in range(2):
-            e("v_bfi_b32 v%d, s%d, v%d, v%d" % (p + i, S_C + 12, p + i, x + i))                                                # copysign(., x)
-        e("v_pk_mul_f32 v[%d:%d], v[%d:%d], 0.5 op_sel_hi:[1,0]" % (x, x + 1, x, x + 1))                                       # h = x / 2
-        e("v_pk_fma_f32 v[%d:%d], v[%d:%d], v[%d:%d], v[%d:%d]" % (x, x + 1, x, x + 1, p, p + 1, x, x + 1))                    # h * erf + h
-
     def gelu_quad(self, xa, ta, xb, tb):
         """Two pairs at once, their instruction streams interleaved (a VALU instruction that reads the result of v_exp_f32 / v_rcp_f32 in
-        the very next issue slot gets the OLD value on gfx950: no interlock). Round 5: gelu(x) = x / (1 + exp2(x Q(x^2))) with a degree-4
+        the very next issue slot gets the OLD value on gfx950: no interlock). gelu(x) = x / (1 + exp2(x Q(x^2))) with a degree-4
         Q - the minimax fit of -log2(e) logit(Phi(x)) / x, leading coefficient of logit side positive so that the sigmoid saturates the
         right way for any |x| - 12 instructions per pair instead of the 18 of the A&S erf form, within 3.4e-6 of gelu(x) over the whole
-        line in fp32 (the fp16 rounding of the result is 5e-4 |y|; fit: tools/r05/gelu_fit.py). `gelu_mode` "packed": the erf form."""
+        line in fp32 (the fp16 rounding of the result is 5e-4 |y|; fit: tools/r05/gelu_fit.py)."""
         e = self.e
-        mode = self.sched.get("gelu_mode", GELU_MODE)
-        if mode != "sigpoly":
-            self.gelu_pair(xa, ta)
-            self.gelu_pair(xb, tb)
-            return
         P = ((xa, ta, ta + 2), (xb, tb, tb + 2))          # (x, u, q) pairs of registers
         for (x, u, q) in P:
             e("v_pk_mul_f32 v[%d:%d], v[%d:%d], v[%d:%d]" % (u, u + 1, x, x + 1, x, x + 1))                                       # u = x^2
@@ -446,15 +396,15 @@ class Gen(AsmWriter):
     F16_BIAS, F16_EM = 180, (96, 128)
     F32_RING, F32_EM = (180, 212, 96), 128
 
-    def resid_loads(self, slab, vm, dest=None):
-        """requests the 32x64 residual slab `slab` (emit layout: pass `it` = four rows, 16 lanes x 16 bytes each). dest: first register
-        of the 32 it lands in - ("v", n) or ("a", n); default: the slab's slot of the VGPR ring"""
+    def resid_loads(self, slab, vm):
+        """requests the 32x64 residual slab `slab` (emit layout: pass `it` = four rows, 16 lanes x 16 bytes each) into its slot of
+        the ring of three VGPR sets"""
         e = self.e
         rb, h = slab >> 1, slab & 1
-        kind, base = dest if dest else ("v", self.F32_RING[slab % 3])
+        base = self.F32_RING[slab % 3]
         for it in range(8):
-            e("buffer_load_dwordx4 %s[%d:%d], v%d, s[%d:%d], 0 offen offset:%d%s" % (kind, base + 4 * it, base + 4 * it + 3, V_R, SRD_R, SRD_R + 3, h * 256,
-                                                                                   self.sched.get("resid_policy", "")))
+            e("buffer_load_dwordx4 v[%d:%d], v%d, s[%d:%d], 0 offen offset:%d%s" % (base + 4 * it, base + 4 * it + 3, V_R, SRD_R, SRD_R + 3, h * 256,
+                                                                                  self.sched.get("resid_policy", "")))
             vm.append(("res", slab))
             if it < 7:
                 e("v_add_u32 v%d, s%d, v%d" % (V_R, S_RROW4, V_R))
@@ -643,13 +593,11 @@ class Gen(AsmWriter):
 
     def epilogue_f32(self, vm):
         e = self.e
-        deep = self.sched.get("deep_ring", False)
         self.c("---- epilogue: out = resid + gamma * (acc + bias) in fp32; eight 32x64 slabs through the wave's 8 KiB; the residual")
         self.c("     slabs come through a ring of three (two requested in the last K-tile, one more ahead of every slab processed).")
-        # sched "deep_ring" (round-4 experiment, off): every parked slab frees 32 ACCUMULATOR registers, which take the slabs 3 / 5 / 7
-        # (a VMEM load may land in AGPRs; four v_accvgpr_read per emit pass bring them to the VALU), the consumed VGPR sets take
-        # 4 / 6: all eight slabs in flight by the time the third is parked. Measured: no change (23.7k vs 24.3k cycles per epilogue
-        # at 65536x1280x1280, wall equal) - the epilogue is not bound by the number of requests a wave's registers can hold.
+        # (A deeper ring was measured and dropped: every parked slab frees 32 accumulator registers, a VMEM load may land in AGPRs, so
+        # all eight slabs can be in flight by the time the third is parked. No change - 23.7k vs 24.3k cycles per epilogue at
+        # 65536x1280x1280, wall equal: the epilogue is not bound by the number of requests a wave's registers can hold.)
         e("s_nop 7")
         if self.m16:
             e("s_nop 7")
@@ -667,16 +615,6 @@ class Gen(AsmWriter):
                 e("v_mov_b32 v%d, 1.0" % (gg + i))
         self.lab(nog)
         em = self.F32_EM
-        R0, R1, R2 = self.F32_RING
-        # where each slab's residual lands, and what is requested at which point of the walk
-        if deep:
-            where = {0: ("v", R0), 1: ("v", R1), 2: ("v", R2), 3: ("a", 0), 4: ("v", R0), 5: ("a", 32), 6: ("v", R1), 7: ("a", 64)}
-            after_park = {0: 3, 1: 5, 2: 7}
-            after_slab = {0: 4, 1: 6}
-        else:
-            where = dict((j, ("v", self.F32_RING[j % 3])) for j in range(8))
-            after_park = {}
-            after_slab = dict((j, j + 3) for j in range(5))
         for slab in range(8):
             rb, h = slab >> 1, slab & 1
             if self.m16:         # 2 x 4 blocks of 4 registers: the lane's columns cbl * 16 + 4 g + 0..3 of the slab are its row's chunk 4 cbl + g
@@ -690,20 +628,13 @@ class Gen(AsmWriter):
                     e("ds_write_b128 v%d, a[%d:%d]" % (V_PARK + cbl * 4 + q, blk, blk + 3))
             for it in range(8):
                 e("ds_read_b128 v[%d:%d], v%d offset:%d" % (em + 4 * it, em + 4 * it + 3, V_EADDR + (it & 3), (it >> 2) * 4096))
-            if slab in after_park:
-                # the first read-back has returned => the parking writes (older, in order) have read the accumulators: these may be overwritten
-                e("s_waitcnt lgkmcnt(7)")
-                self.resid_loads(after_park[slab], vm, where[after_park[slab]])
-            kind, rbase = where[slab]
+            rbase = self.F32_RING[slab % 3]
             bb, gg = (V_BG0, V_GG0) if h == 0 else (V_BG1, V_GG1)
             e("s_waitcnt vmcnt(%d)" % self.younger(vm, ("res", slab)))
             for it in range(8):
-                if kind == "a":            # residual pass `it` from its accumulator registers into the idle VGPR set
-                    for i in range(4):
-                        e("v_accvgpr_read_b32 v%d, a%d" % (R2 + 4 * it + i, rbase + 4 * it + i))
                 e("s_waitcnt lgkmcnt(%d)" % (7 - it))
                 r = em + 4 * it
-                rr = (R2 if kind == "a" else rbase) + 4 * it
+                rr = rbase + 4 * it
                 for half in range(2):
                     e("v_pk_add_f32 v[%d:%d], v[%d:%d], v[%d:%d]" % (r + 2 * half, r + 2 * half + 1, r + 2 * half, r + 2 * half + 1, bb + 2 * half, bb + 2 * half + 1))
                 for half in range(2):
@@ -725,8 +656,8 @@ class Gen(AsmWriter):
             if self.lnp:
                 for vv, r28, r4 in ((V_O16, S_O16ROW28, S_O16ROW4), (V_ST, S_STROW28, S_STROW4)):
                     e(("v_subrev_u32 v%d, s%d, v%d" if h == 0 else "v_add_u32 v%d, s%d, v%d") % (vv, r28 if h == 0 else r4, vv))
-            if slab in after_slab:      # the VGPR set just consumed takes a later slab
-                self.resid_loads(after_slab[slab], vm, where[after_slab[slab]])
+            if slab < 5:                # the VGPR set just consumed takes the slab three on
+                self.resid_loads(slab + 3, vm)
 
     def lnp_setup(self):
         e = self.e
@@ -753,20 +684,13 @@ class Gen(AsmWriter):
         """folded-LayerNorm producer: v[r:r+3] = four consecutive final values of one row (16 lanes hold the row's 64 columns of this
         slab): their fp16 copy goes to out16, the row's (sum, sum of squares) over the 64 columns to stats[row][column group]."""
         e = self.e
-        abl = self.sched.get("lnp_ablate", "")          # experiments: "valu" / "st16" / "stst" parts left out (results wrong)
-        if "valu" in abl:
-            e("v_cvt_pk_f16_f32 v%d, v%d, v%d" % (V_SQ, r, r + 1))
-            e("v_cvt_pk_f16_f32 v%d, v%d, v%d" % (V_SQ + 1, r + 2, r + 3))
-        if "valu" not in abl:
-            self.ln_producer_valu(r)
-        if "st16" not in abl:
-            e("buffer_store_dwordx2 v[%d:%d], v%d, s[%d:%d], 0 offen offset:%d%s" % (V_SQ, V_SQ + 1, V_O16, SRD_O16, SRD_O16 + 3, h * 128, self.sched.get("store16_policy", "")))
-            vm.append(("st", slab))
-        if "stst" not in abl:
-            e("s_mov_b64 exec, s[%d:%d]" % (S_EXROW, S_EXROW + 1))
-            e("buffer_store_dwordx2 v[%d:%d], v%d, s[%d:%d], 0 offen offset:%d" % (V_SUM, V_SUM + 1, V_ST, SRD_ST, SRD_ST + 3, h * 8))
-            vm.append(("st", slab))
-            e("s_mov_b64 exec, -1")
+        self.ln_producer_valu(r)
+        e("buffer_store_dwordx2 v[%d:%d], v%d, s[%d:%d], 0 offen offset:%d%s" % (V_SQ, V_SQ + 1, V_O16, SRD_O16, SRD_O16 + 3, h * 128, self.sched.get("store16_policy", "")))
+        vm.append(("st", slab))
+        e("s_mov_b64 exec, s[%d:%d]" % (S_EXROW, S_EXROW + 1))
+        e("buffer_store_dwordx2 v[%d:%d], v%d, s[%d:%d], 0 offen offset:%d" % (V_SUM, V_SUM + 1, V_ST, SRD_ST, SRD_ST + 3, h * 8))
+        vm.append(("st", slab))
+        e("s_mov_b64 exec, -1")
 
     def ln_producer_valu(self, r):
         e = self.e
@@ -952,21 +876,11 @@ class Gen(AsmWriter):
             e("v_lshlrev_b32 v%d, 2, v%d" % (V_T3, V_LG))
             e("v_add_u32 v%d, s%d, v%d" % (V_T3, S_T2, V_T3))
             e("v_lshlrev_b32 v%d, 2, v%d" % (V_TMP + 11, V_T3))
-        if self.epi == EPI_GELU_F16 and self.sched.get("gelu_mode", GELU_MODE) == "sigpoly":
-            # -log2(e) Q(u), Q of gelu_quad: [0:1] c4, [2:3] c2, [4:5] c1, [6:7] c0 (c3 lives in two VGPRs: one SGPR operand per instruction)
-            consts = [0xb658b1ce, 0xb658b1ce, 0x39bce2fa, 0x39bce2fa, 0xbdd78116, 0xbdd78116, 0xc01354b6, 0xc01354b6]
-            for i, cst in enumerate(consts):
+        if self.epi == EPI_GELU_F16:                # the polynomial of gelu_quad: [0:1] c4, [2:3] c2, [4:5] c1, [6:7] c0; c3 in two VGPRs
+            for i, cst in enumerate(GELU_SGPR_CONSTS):
                 e("s_mov_b32 s%d, 0x%08x" % (S_C + i, cst))
-            e("v_mov_b32 v%d, 0x38b90ca2" % (V_TMP + 8))
-            e("v_mov_b32 v%d, 0x38b90ca2" % (V_TMP + 9))
-        elif self.epi == EPI_GELU_F16:
-            # [0] p / sqrt(2), [2:3] a5, [4:5] -log2(e) / 2, [6:7] a3, [8:9] a2, [10:11] a1, [12] abs mask (a4 lives in two VGPRs)
-            consts = [0x3e6d3388, 0x3e6d3388, 0x3f87dc22, 0x3f87dc22, 0xbf38aa3b, 0xbf38aa3b, 0x3fb5f0e3, 0x3fb5f0e3,
-                      0xbe91a98e, 0xbe91a98e, 0x3e827906, 0x3e827906, 0x7fffffff]
-            for i, cst in enumerate(consts):
-                e("s_mov_b32 s%d, 0x%08x" % (S_C + i, cst))
-            e("v_mov_b32 v%d, 0xbfba00e3" % (V_TMP + 8))
-            e("v_mov_b32 v%d, 0xbfba00e3" % (V_TMP + 9))
+            e("v_mov_b32 v%d, 0x%08x" % (V_TMP + 8, GELU_C3))
+            e("v_mov_b32 v%d, 0x%08x" % (V_TMP + 9, GELU_C3))
         if self.lnp:
             # kernarg 104: out16 pointer, 112: stats pointer, 120: ld16
             e("s_load_dwordx4 s[%d:%d], s[0:1], 0x68" % (SRD_O16, SRD_O16 + 3))
@@ -1007,27 +921,6 @@ class Gen(AsmWriter):
         e("s_waitcnt lgkmcnt(0)")
         e("s_cmp_eq_u32 s%d, -1" % S_TNEXT)
         e("s_cbranch_scc1 L_exit_%s" % n)
-        if self.sched.get("stagger"):
-            # start-time stagger (experiment): workgroup group g = (wg >> 3) % groups (workgroup b runs on XCD b % 8: every XCD has
-            # all groups) idles g * units * 64 * 127 cycles first, so that the groups' epilogue bursts do not coincide
-            groups, units = self.sched["stagger"]
-            lp, done = self.u("L_stag"), self.u("L_stag_done")
-            if self.sched.get("stagger_by") == "xcd":
-                # round 6: the two groups are the two HALVES OF THE CHIP (XCDs 0..3 / 4..7; workgroup b runs on XCD b % 8): one half's
-                # epilogue traffic then meets the other half's k-loops in HBM / the fabric, but not in their L2s
-                assert groups == 2
-                e("s_bfe_u32 s%d, s%d, 0x10002" % (S_T0, S_WG))
-            else:
-                e("s_lshr_b32 s%d, s%d, 3" % (S_T0, S_WG))
-                e("s_and_b32 s%d, s%d, %d" % (S_T0, S_T0, groups - 1))
-            e("s_mul_i32 s%d, s%d, %d" % (S_T0, S_T0, units))
-            self.lab(lp)
-            e("s_cmp_eq_u32 s%d, 0" % S_T0)
-            e("s_cbranch_scc1 %s" % done)
-            e("s_sleep 127")
-            e("s_sub_u32 s%d, s%d, 1" % (S_T0, S_T0))
-            e("s_branch %s" % lp)
-            self.lab(done)
         self.switch_tile()
         for kt in range(2):
             for p in range(16):
@@ -1132,30 +1025,27 @@ class Gen(AsmWriter):
             e("s_add_u32 s%d, s%d, s%d" % (S_ACC_LOOP, S_ACC_LOOP, S_T0))
             e("s_add_u32 s%d, s%d, s%d" % (S_NKT, S_NKT, S_NK))
         # memory operations between the operand requests of the last K-tile and the epilogue: that K-tile's DMA pieces
-        n_dma_after = 0 if self.sched.get("no_dma") else sum(1 for p in range(16) if self.sched["dma"][p] > self.sched.get("pre_slot", 17))
+        n_dma_after = sum(1 for p in range(16) if self.sched["dma"][p] > self.sched.get("pre_slot", 17))
         assert not self.m16 or n_dma_after in (0, 16)
-        if self.sched.get("no_epilogue"):
-            pass
-        else:
+        pre_lines = self.L
+        self.L = []
+        vm = self.pre_epilogue()
+        self.pre_code = self.L
+        self.L = pre_lines
+        # (the 16x16x32 form requests the folded-LayerNorm operands with the others: all sixteen pieces follow)
+        n_late = n_dma_after if self.m16 else sum(1 for p in range(16) if self.sched["dma"][p] > 48)
+        vm += [("dma", 0)] * (n_dma_after - n_late)
+        if self.lnc:
             pre_lines = self.L
             self.L = []
-            vm = self.pre_epilogue()
-            self.pre_code = self.L
+            vm += self.pre2_epilogue()
+            self.pre2_code = self.L
             self.L = pre_lines
-            # (the 16x16x32 form requests the folded-LayerNorm operands with the others: all sixteen pieces follow)
-            n_late = n_dma_after if self.m16 else 0 if self.sched.get("no_dma") else sum(1 for p in range(16) if self.sched["dma"][p] > 48)
-            vm += [("dma", 0)] * (n_dma_after - n_late)
-            if self.lnc:
-                pre_lines = self.L
-                self.L = []
-                vm += self.pre2_epilogue()
-                self.pre2_code = self.L
-                self.L = pre_lines
-            vm += [("dma", 0)] * n_late
-            if self.epi == EPI_F32:
-                self.epilogue_f32(vm)
-            else:
-                self.epilogue_f16(self.epi == EPI_GELU_F16, vm)
+        vm += [("dma", 0)] * n_late
+        if self.epi == EPI_F32:
+            self.epilogue_f32(vm)
+        else:
+            self.epilogue_f16(self.epi == EPI_GELU_F16, vm)
         if self.sched.get("trace"):
             e("s_memtime s[%d:%d]" % (S_TS0, S_TS0 + 1))
             e("s_waitcnt lgkmcnt(0)")
@@ -1202,16 +1092,15 @@ class Gen(AsmWriter):
             self.lab("L_switch_z_%s" % n)
             self.switch_tile()
             e("s_branch L_switch_ret_z_%s" % n)
-        if not self.sched.get("no_epilogue"):
-            self.lab("L_pre_%s" % n)
-            self.L += self.pre_code
-            if self.lnc and self.m16:
-                self.L += self.pre2_code
-            e("s_branch L_pre_ret_%s" % n)
-            if self.lnc and not self.m16:
-                self.lab("L_pre2_%s" % n)
-                self.L += self.pre2_code
-                e("s_branch L_pre2_ret_%s" % n)
+        self.lab("L_pre_%s" % n)
+        self.L += self.pre_code
+        if self.lnc and self.m16:
+            self.L += self.pre2_code
+        e("s_branch L_pre_ret_%s" % n)
+        if self.lnc and not self.m16:
+            self.lab("L_pre2_%s" % n)
+            self.L += self.pre2_code
+            e("s_branch L_pre2_ret_%s" % n)
         self.L += kernel_end(n, 163840, 128 if self.lnp else 104, NUM_SGPR)
 
     def metadata(self):
@@ -1254,60 +1143,17 @@ def m16_sched(base=None):
                 rd0=free[:16], adv=free[16])             # the next K-tile's k-step 0 in the free gaps behind barrier B, then the nine SALU of the advance
 
 
-def experiment_scheds():
-    """numbered variants for tools/gemm_asm_ab.py (kernel names get the suffix _v<i>); 0 is the shipped schedule"""
-    out = []
-    b = default_sched()
-    out.append(dict(b, trace=True))                                                   # 1: shipped schedule + trace
-    out.append(dict(b, trace=True, no_epilogue=True))                                 # 2: no epilogue (results wrong)
-    out.append(dict(b, trace=True, no_epilogue=True, no_dma=True))                    # 3: + no DMA
-    out.append(dict(b, trace=True, no_epilogue=True, no_dma=True, no_reads=True))     # 4: + no fragment reads: MFMAs + barriers
-    out.append(dict(b, trace=True, no_epilogue=True, no_dma=True, no_reads=True, no_barrier=True))   # 5: MFMAs only
-    out.append(dict(b, trace=True, no_epilogue=True, no_reads=True))                  # 6: DMA + MFMAs, no fragment reads
-    out.append(dict(b, trace=True, dma=[21 + p for p in range(16)], barB=46))         # 7: DMA pieces in consecutive slots
-    out.append(dict(b, trace=True, dma=[21 + 2 * p for p in range(16)], barB=46))     # 8: one piece per two slots (last at 51)
-    out.append(dict(b, trace=True, rd23=[i // 2 for i in range(16)], barA=17, dma=[19 + (3 * p) // 2 for p in range(16)]))   # 9: S2/S3 reads two per slot, earlier barrier A
-    out.append(dict(b, trace=True, prio=1))                                           # 10
-    out.append(dict(b, trace=True))                                                   # 11: (was: GELU one element per instruction - 24.0k vs 20.5k cycles)
-    out.append(dict(b, trace=True, gelu_mode="notrans"))                              # 12: packed, v_rcp / v_exp replaced by moves (timing only)
-    out.append(dict(b, trace=True, gelu_mode="none"))                                 # 13: no GELU arithmetic at all
-    out.append(dict(b, trace=True, dma=[21 + (5 * p) // 2 for p in range(16)]))       # 14: one piece per 2.5 slots (last at 58)
-    out.append(dict(b, trace=True, dma=[21 + (11 * p) // 4 for p in range(16)]))      # 15: one per 2.75 slots (last at 62)
-    out.append(dict(b, trace=True, resid_policy=""))                                  # 16: fp32 epilogue: residual loads with the default cache policy
-    out.append(dict(b, trace=True, store_policy=""))                                  # 17: stores with the default cache policy
-    out.append(dict(b, trace=True, store_policy=" sc0 sc1"))                          # 18: stores with system scope (write-through)
-    out.append(dict(b, trace=True, store_policy=" sc0 sc1 nt", resid_policy=" sc0 sc1 nt"))   # 19
-    out.append(dict(b, resid_policy=""))                                              # 20: untraced: default-policy residual loads
-    out.append(dict(b, store_policy=""))                                              # 21: untraced: default-policy stores
-    out.append(dict(b, trace=True, store_policy=""))                                  # 22: = 17
-    out.append(dict(b, store_policy=" sc1"))                                          # 23
-    out.append(dict(b, store_policy=" sc0 sc1"))                                      # 24
-    out.append(dict(b, trace=True, deep_ring=True))                                   # 25: fp32 epilogue: residual slabs also through freed accumulator registers (all 8 in flight early): no change
-    # start-time stagger (so that the workgroups' epilogue bursts do not coincide): nothing gained on any of the four SAM shapes
-    # (65536x1280x1280: 897 / 850 unstaggered vs 888 / 876, 788 / 865, 739 / 860, 743 / 854, 755 / 824 TFLOP/s)
-    out.append(dict(b, stagger=(2, 2)))                                               # 26: two start groups, 16k cycles apart (untraced)
-    out.append(dict(b, stagger=(4, 1)))                                               # 27: four groups, 8k cycles apart
-    out.append(dict(b, stagger=(2, 1)))                                               # 28: two groups, 8k cycles apart
-    out.append(dict(b, stagger=(4, 2)))                                               # 29: four groups, 16k apart
-    out.append(dict(b, stagger=(8, 1)))                                               # 30: eight groups, 8k apart
-    out.append(dict(b, trace=True, pre_slot=47))                                      # 31: epilogue operands requested BEHIND barrier B of the last K-tile (its vmcnt no longer waits for them)
-    out.append(dict(b, pre_slot=47))                                                  # 32: the same, untraced
-    out.append(dict(b, resid_policy=" sc1"))                                          # 33-35: residual loads with other cache policies (untraced)
-    out.append(dict(b, resid_policy=" sc0 sc1"))
-    out.append(dict(b, resid_policy=" sc1 nt"))
-    out.append(dict(b, gelu_mode="none"))                                             # 36: untraced: no GELU arithmetic (timing only: what a free GELU would buy under the power cap)
-    out.append(dict(b, gelu_mode="notrans"))                                          # 37: untraced: the packed GELU without its transcendentals
-    # 38-42 (round 6): start-time stagger between the two halves of the chip (XCDs 0..3 start 16k / 24k / 32k / 40k / 48k cycles before
-    # XCDs 4..7): if the fp32 epilogues are bound by what the memory system gives 256 CUs at once, halves that alternate get twice the share.
-    # Measured (tools/gemm_asm_ab.py 0,26,38..42, TFLOP/s, two passes): 65536x1280x1280 shipped 884 / 849, staggered 719-861; 65536x1280x5120
-    # 1153 / 1178 against 1144-1183; 131072x1280x1280 910 / 891 against 887-913 - nothing: the epilogue's ~24 bytes per cycle and CU are not a
-    # share of a saturated memory system (the other half of the chip being in its k-loops does not make it faster)
-    for u in (2, 3, 4, 5, 6):
-        out.append(dict(b, stagger=(2, u), stagger_by="xcd"))
-    return out
+# Measured against these schedules and dropped: a start-time stagger of the workgroups, so that their epilogue bursts do not coincide.
+# 2 / 4 / 8 groups 8k or 16k cycles apart (every XCD holds all groups): 65536x1280x1280 897 / 850 TFLOP/s unstaggered against
+# 739-888 / 824-876. The two halves of the chip (XCDs 0..3 / 4..7) 16k ... 48k cycles apart: 884 / 849 against 719-861,
+# 65536x1280x5120 1153 / 1178 against 1144-1183, 131072x1280x1280 910 / 891 against 887-913. Nothing on any of the four SAM shapes: the
+# epilogue's ~24 bytes per cycle and CU are not a share of a saturated memory system (the other half of the chip being in its k-loops
+# does not make it faster).
 
 
-def variants():
+def variants(trace=False):
+    """(kernel name, epilogue, schedule) of every kernel of the library; trace: also the `_v1` forms that count cycles per K-tile loop
+    and per epilogue (tools/gemm_asm_ab.py reads them back; psam_gemm_asm_variant(1) selects them)"""
     base = default_sched()
     out = [("psam_gemm_asm_f16", EPI_F16, base), ("psam_gemm_asm_gelu", EPI_GELU_F16, base), ("psam_gemm_asm_f32", EPI_F32, base)]
     # the same kernels with the default cache policy for the epilogue's loads and stores: for outputs the next launch finds in the L2
@@ -1315,9 +1161,9 @@ def variants():
     keep = dict(base, resid_policy="", store_policy="")
     out += [("psam_gemm_asm_f16_l2", EPI_F16, keep), ("psam_gemm_asm_gelu_l2", EPI_GELU_F16, keep), ("psam_gemm_asm_f32_l2", EPI_F32, keep)]
     # LayerNorm folded into the GEMMs either side of it (psam_gemm_f16_ln): consumers (fp16 / GELU) and the producer (fp32)
-    # (producer ablations, 65536x1280x1280 / x5120 TFLOP/s, plain kernel 785 / 1169: full 741 / 1145 - without the fp16 copy's stores
-    # 787 / 1166, without the statistics' stores 756 / 1133, without their arithmetic 732 / 1140, without all three 815 / 1178:
-    # sched key "lnp_ablate")
+    # (what the producer's extra work costs, 65536x1280x1280 / x5120 TFLOP/s, plain kernel 785 / 1169: full 741 / 1145 - without the
+    # fp16 copy's stores 787 / 1166, without the statistics' stores 756 / 1133, without their arithmetic 732 / 1140, without all
+    # three 815 / 1178)
     # split-K form of the fp32 kernel (round 6): items are (tile, K range), the partial sums of a range go to its plane of the workspace
     # (default cache policy: the reduce pass behind it reads them from the L2 / memory-side cache)
     out += [("psam_gemm_asm_f32_sk", EPI_F32, dict(keep, splitk=True))]
@@ -1326,25 +1172,25 @@ def variants():
     # the same tile on v_mfma_f32_16x16x32_f16 (csrc/gemm.hip tile 17): plain and folded-LayerNorm forms
     out += [("psam_gemm_asm_f16_m16", EPI_F16, m16_sched(base)), ("psam_gemm_asm_gelu_m16", EPI_GELU_F16, m16_sched(base)), ("psam_gemm_asm_f32_m16", EPI_F32, m16_sched(base))]
     out += [("psam_gemm_asm_f16_ln_m16", EPI_F16, m16_sched(ln)), ("psam_gemm_asm_gelu_ln_m16", EPI_GELU_F16, m16_sched(ln)), ("psam_gemm_asm_f32_ln_m16", EPI_F32, m16_sched(ln))]
-    if "--experiments" in sys.argv:
-        for nm, epi in (("f16", EPI_F16), ("gelu", EPI_GELU_F16), ("f32", EPI_F32)):     # _m16_v1: the 16x16x32 schedule + trace
-            out.append(("psam_gemm_asm_%s_m16_v1" % nm, epi, m16_sched(dict(base, trace=True))))
-        for i, sc in enumerate(experiment_scheds()):
-            for nm, epi in (("f16", EPI_F16), ("gelu", EPI_GELU_F16), ("f32", EPI_F32)):
-                out.append(("psam_gemm_asm_%s_v%d" % (nm, i + 1), epi, sc))
+    if trace:
+        traced = dict(base, trace=True)
+        for suffix, sc in (("_m16_v1", m16_sched(traced)), ("_v1", traced)):
+            out += [("psam_gemm_asm_f16" + suffix, EPI_F16, sc), ("psam_gemm_asm_gelu" + suffix, EPI_GELU_F16, sc), ("psam_gemm_asm_f32" + suffix, EPI_F32, sc)]
     return out
 
 
 def main():
+    """no argument: the module of the library; --trace: with the traced `_v1` kernels; --meta: the header gemm_asm_meta.h"""
+    trace = "--trace" in sys.argv[1:]
     import gemm_asm2_gen                      # the half-tile ping-pong kernels (tile 16) live in the same code object
-    l2, meta2, es = gemm_asm2_gen.build_all()
-    if "--meta" in sys.argv:                  # header for csrc/gemm.hip: K-tile iterations the hidden epilogues need
+    l2, meta2, es = gemm_asm2_gen.build_all(trace)
+    if "--meta" in sys.argv[1:]:                  # header for csrc/gemm.hip: K-tile iterations the hidden epilogues need
         out = ["// generated by gemm_asm_gen.py --meta: a half-tile's epilogue is spread over E K-tile iterations of the next one"]
         for nm in ("f16", "gelu", "f32"):
             out.append("#define PSAM_ASM2_E_%s %d" % (nm.upper(), es["psam_gemm_asm2_" + nm]))
         sys.stdout.write("\n".join(out) + "\n")
         return
-    ks = variants()
+    ks = variants(trace)
     lines = []
     meta = []
     for name, epi, sc in ks:

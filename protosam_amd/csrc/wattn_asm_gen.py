@@ -22,7 +22,7 @@ This kernel does the same work in ~700, with a different arrangement of the wind
     probabilities packed in place into the score registers (the B operand of the P V product as they stand), row sums by an all-ones
     MFMA, fragment reads several fragments ahead through one register ring.
 
-Measured (16 slices: 6400 items, us per call; HIP wattn_p_kernel on the same box 340-355): 308. Ablations (PSAM_GEN_WATTN_ABLATE, results
+Measured (16 slices: 6400 items, us per call; HIP wattn_p_kernel on the same box 340-355): 308. With parts left out (results
 wrong): without the two barriers per item 273, without the K / V DMA 248, without both 218 (= the instruction streams alone), without any
 arithmetic (DMA, query loads, stores, barriers only) 198, without the rel-pos prologue 270, without softmax 267, without P V / scores
 277 / 273: the memory side and the arithmetic each take ~200 us and overlap only in part. Tried: the three images rotating (K, V,
@@ -81,12 +81,7 @@ A_Q, A_RING, A_ONES, A_O, A_L = 0, 12, 36, 40, 60
 RING = 6                          # fragment slots of four registers: a12..35
 AH = 4                            # fragments requested ahead of their use
 
-import os
-
 from asm_common import AsmWriter, LdsCounter, kernel_begin, kernel_end, kernel_metadata, module_text
-
-LAZYMAX = os.environ.get("PSAM_GEN_WATTN_LAZYMAX", "1") != "0"      # cross-lane row maxima only in the first chunk and inside a rescale
-ABL = os.environ.get("PSAM_GEN_WATTN_ABLATE", "")      # timing experiments (results wrong): nobar, nodma, nosoft, noprol, nopv, noqk
 
 
 class GenW(AsmWriter):
@@ -412,7 +407,7 @@ class GenW(AsmWriter):
         # the four lanes of a query hold different keys: the first chunk reduces its maxima across them (the running maximum starts
         # there); later chunks compare per lane - the offset only has to keep the exponentials in range - and reduce inside the
         # (rare) rescale
-        for swap in (("v_permlane16_swap_b32", "v_permlane32_swap_b32") if first or not LAZYMAX else ()):
+        for swap in (("v_permlane16_swap_b32", "v_permlane32_swap_b32") if first else ()):
             raw("v_mov_b32 v%d, v%d" % (V_T5, V_MX))
             raw("v_mov_b32 v%d, v%d" % (V_T6, V_MX))
             raw("s_nop 1")
@@ -445,9 +440,8 @@ class GenW(AsmWriter):
             raw("v_cvt_pk_f16_f32 v%d, v%d, v%d" % (a + 3, b + 2, b + 3))
         if first:
             # V of this item complete in every wave: the only younger requests of this wave are the next item's six K pieces
-            if "nobar" not in ABL:
-                raw("s_waitcnt vmcnt(3)")      # (three or six K pieces of the next item are younger)
-                raw("s_barrier")
+            raw("s_waitcnt vmcnt(3)")          # (three or six K pieces of the next item are younger)
+            raw("s_barrier")
         raw("s_nop 4")            # VALU write (the packed probabilities) -> MFMA operand read: wait states (the MFMA reads stale data otherwise)
         for uu in range(nt // 2):
             u = T0 // 2 + uu
@@ -459,18 +453,12 @@ class GenW(AsmWriter):
                 o = A_O + 4 * dt
                 fmt = "v_mfma_f32_16x16x32_f16 a[%d:%d], %%s, v[%d:%d], %s" % (o, o + 3, p, p + 3, "0" if zero else "a[%d:%d]" % (o, o + 3))
                 B.append(("mfma", (fmt, self.v_frag(u, dt))))
-        if "nosoft" in ABL:
-            A = [op for op in A if op[0] != "raw" or not op[1].startswith(("v_", "s_cbranch_vccnz", "s_nop 1"))]
-        if "noqk" in ABL:
-            A = [op for op in A if op[0] != "mfma"]
-        if "nopv" in ABL:
-            B = []
         return A, B
 
     def rescale_routine(self, tag):
         e = self.e
         self.lab("L_resc_%s_%s" % (tag, self.name))
-        for swap in (("v_permlane16_swap_b32", "v_permlane32_swap_b32") if LAZYMAX else ()):
+        for swap in ("v_permlane16_swap_b32", "v_permlane32_swap_b32"):
             e("v_mov_b32 v%d, v%d" % (V_T5, V_MX))
             e("v_mov_b32 v%d, v%d" % (V_T6, V_MX))
             e("s_nop 1")
@@ -656,10 +644,8 @@ class GenW(AsmWriter):
         self.ldsq.n, self.ldsq.done, self.frag_n = 0, -1, 0
         # requests for the next item: its K image into the other buffer
         self.scalars_dma(S_ENTN)
-        if "nodma" not in ABL:
-            self.dma_image(0, S_KNXT, None)
-        if "noprol" not in ABL:
-            self.prologue_relpos()
+        self.dma_image(0, S_KNXT, None)
+        self.prologue_relpos()
 
         def after_last_qk():
             # the query fragments of the next item may land in the registers now (no score MFMA of this item is left)
@@ -704,14 +690,12 @@ class GenW(AsmWriter):
         e("s_mov_b64 exec, -1")
         # ---- end of the item: the next item's K pieces (older than its 3 query loads and the 5 stores) have landed; every wave is
         #      done with K / V of this item
-        if "nobar" not in ABL:
-            e("s_waitcnt vmcnt(8)")
-            e("s_barrier")
+        e("s_waitcnt vmcnt(8)")
+        e("s_barrier")
         e("s_cmp_eq_u32 s%d, -1" % S_ENTN)
         e("s_cbranch_scc1 L_exit_%s" % n)
         # V of the next item (the descriptors of the loaded item are still set), then advance
-        if "nodma" not in ABL:
-            self.dma_image(1, None, V_BASE)
+        self.dma_image(1, None, V_BASE)
         e("s_mov_b32 s%d, s%d" % (S_T0, S_KCUR))
         e("s_mov_b32 s%d, s%d" % (S_KCUR, S_KNXT))
         e("s_mov_b32 s%d, s%d" % (S_KNXT, S_T0))
@@ -723,7 +707,7 @@ class GenW(AsmWriter):
         e("s_add_u32 s%d, s%d, s%d" % (S_CUR, S_CUR, S_STRIDE))
         e("s_load_dword s%d, s[%d:%d], s%d" % (S_ENTN, S_WORK, S_WORK + 1, S_CUR))
         # the query fragments of the new item (requested before the five stores, the barrier and the V pieces)
-        e("s_waitcnt vmcnt(%d) lgkmcnt(0)" % (0 if "nodma" in ABL else 8))   # (five stores and three or six V pieces are younger)
+        e("s_waitcnt vmcnt(8) lgkmcnt(0)")   # (five stores and three or six V pieces are younger)
         e("s_branch L_item_%s" % n)
         self.lab("L_exit_%s" % n)
         e("s_waitcnt vmcnt(0) lgkmcnt(0)")

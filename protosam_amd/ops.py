@@ -325,7 +325,8 @@ def gemm_set_option(name, value):
 
 
 def gemm_asm_variant(v):
-    """Experiment kernels of the assembly GEMM (library built with GENFLAGS=--experiments); 0 = shipped schedule."""
+    """0 = the shipped assembly GEMM kernels; 1 = their traced forms (cycles per K-tile loop and per epilogue), which only a library
+    built with `make GENFLAGS=--trace` holds: without them the next GEMM raises."""
     _bump_dispatch()
     _lib.check(_lib.lib().psam_gemm_asm_variant(int(v)), "psam_gemm_asm_variant")
 

@@ -786,8 +786,8 @@ def test_gemm_folded_layernorm(dev, tile, M, D, N2, act):
 @pytest.mark.parametrize("M,N,K", [(256, 256, 128), (4096, 1280, 1280), (33000, 1280, 192), (70001, 768, 128), (2000, 1280, 5120)])
 @pytest.mark.parametrize("ln", [0, 1])
 def test_gemm_fp32_residual_without_gamma(dev, M, N, K, ln):
-    """Tile 15's fp32 epilogue as the SAM encoder calls it (no gamma; in place): its residual slabs travel through the VGPR ring AND
-    through accumulator registers freed by the parked slabs (gemm_asm_gen.py epilogue_f32) - every slab position must get its own rows.
+    """Tile 15's fp32 epilogue as the SAM encoder calls it (no gamma; in place): its eight residual slabs travel through a ring of three
+    VGPR sets, each refilled as soon as it is consumed (gemm_asm_gen.py epilogue_f32) - every slab position must get its own rows.
     Bit-identical to the HIP kernel (tile 11: same arithmetic in the same order), out of place, without a residual, and as the
     folded-LayerNorm producer (fp16 copy + row sums)."""
     from protosam_amd import ops

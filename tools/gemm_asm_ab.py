@@ -1,12 +1,15 @@
-"""A/B of the assembly GEMM's experiment variants (library built with `make -C protosam_amd/csrc GENFLAGS=--experiments`):
-  PSAM_GEMM_ASM_TRACE=1 python tools/gemm_asm_ab.py 0,1,2,... [MxNxKxEPI;...]
-variant 0 = shipped schedule, t11 = the HIP persistent kernel; the trace lines (stderr) give cycles per K-tile / per epilogue."""
+"""The assembly GEMM against the HIP persistent kernel, and its traced forms (library built with
+`make -C protosam_amd/csrc GENFLAGS=--trace`):
+  PSAM_GEMM_ASM_TRACE=1 python tools/gemm_asm_ab.py [0,1] [MxNxKxEPI;...]
+variant 0 = the shipped kernels, 1 = their traced forms, t11 = the HIP persistent kernel; the trace lines (stderr) give cycles per
+K-tile / per epilogue. A candidate schedule is compared as a second library build: run this once per library, PSAM_LIB_PATH naming it."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from protosam_amd import ops
 dev = torch.device("cuda:0")
 variants = [int(v) for v in (sys.argv[1] if len(sys.argv) > 1 else "0,1").split(",")]
+assert set(variants) <= {0, 1}, "variants: 0 (shipped) and 1 (traced)"
 shapes = sys.argv[2] if len(sys.argv) > 2 else "65536x3840x1280x0;65536x5120x1280x1;65536x1280x5120x2;65536x1280x1280x2;8192x8192x8192x0"
 
 

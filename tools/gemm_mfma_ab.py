@@ -7,8 +7,9 @@ both and whether tile 17's median beats tile 15's by more than the min-max sprea
 mfma16_auto is written from).
   python tools/gemm_mfma_ab.py [rounds] [plain]         -> the table (stdout); "plain": the same shapes without the LayerNorm fold
 Each shape warms both tiles up (20 calls each, not measured) before its first round.
-With a library / code object built with GENFLAGS=--experiments and PSAM_GEMM_ASM_TRACE=1 it instead runs the plain (not
-LayerNorm-folded) forms of the same shapes once per tile on the traced variant 1: cycles per K-tile and per epilogue on stderr."""
+With a library built with GENFLAGS=--trace and PSAM_GEMM_ASM_TRACE=1 it instead runs the plain (not LayerNorm-folded) forms of the
+same shapes once per tile on the traced variant 1: cycles per K-tile and per epilogue on stderr. A candidate build is compared as a
+second library: one run per library, PSAM_LIB_PATH naming it."""
 import os
 import statistics
 import sys

@@ -1,5 +1,6 @@
 """Round 5: the four SAM ViT-H block GEMMs at 16 slices as the pipeline launches them (folded-LayerNorm forms), us per launch and
-TFLOP/s, for A/B of code objects (PSAM_GEMM_ASM_CO=build/<variant>.co).   python tools/r05/gemm_shapes_time.py"""
+TFLOP/s. A/B of a candidate build goes through two libraries: one run per library, PSAM_LIB_PATH naming it.
+python tools/r05/gemm_shapes_time.py"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import torch
@@ -47,4 +48,4 @@ for n, fn, fl in cases:
     t = sorted(res[n])[1]
     tot += t
     out.append(f"{n} {t:6.1f} us {fl / t / 1e6:5.0f} TF/s")
-print(f"{os.environ.get('PSAM_GEMM_ASM_CO', 'shipped'):>22}: " + " | ".join(out) + f" | block sum {tot:.0f} us", flush=True)
+print(f"{os.environ.get('PSAM_LIB_PATH', 'shipped')[-22:]:>22}: " + " | ".join(out) + f" | block sum {tot:.0f} us", flush=True)
