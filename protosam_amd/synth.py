@@ -91,6 +91,40 @@ def heavy_tail_sam_(sd, seed=1234, parts=("scale", "massive", "student")):
     return sd
 
 
+def heavy_tail_dino_(sd, seed=1234, pre=""):
+    """In place: the DINOv2 counterpart of `heavy_tail_sam_` for a synthetic hub-named state dict (keys under `pre`): per-channel scales
+    exp(N(0, 1)) clamped to [0.25, 8] on the patch embedding and `pos_embed`, three 'massive activation' channels in `pos_embed` (+-30
+    at every token, +-250 more at six token positions), LayerScale gammas spread over two decades (10^U(-1.5, 0.5) per channel),
+    Student-t (3 degrees of freedom) `attn.proj` / `mlp.fc2` weights scaled 0.7 / sqrt(fan_in), and register tokens times 8: outlier
+    tokens and channels in the hundreds for the fp16 copy, the sum-of-squares statistics and the -mean operands of the folded LayerNorm."""
+    g = _gen(seed, "heavy_tail_dino")
+    pe = sd[pre + "pos_embed"]
+    D = pe.shape[-1]
+    scale = torch.exp(torch.randn(D, generator=g)).clamp(0.25, 8.0)
+    sd[pre + "patch_embed.proj.weight"] *= scale[:, None, None, None]
+    sd[pre + "patch_embed.proj.bias"] *= scale
+    pe *= scale
+    for c in torch.randperm(D, generator=g)[:3].tolist():
+        sign = 1.0 if c % 2 == 0 else -1.0
+        pe[..., c] += sign * 30.0
+        for _ in range(6):
+            pe[0, int(torch.randint(0, pe.shape[1], (1,), generator=g)), c] += sign * 250.0
+    for k in sd:
+        if not k.startswith(pre + "blocks."):
+            continue
+        g = _gen(seed, "heavy_tail_dino." + k[len(pre):])      # (per name: block i is the same whatever the depth of the model)
+        if k.endswith("ls1.gamma") or k.endswith("ls2.gamma"):
+            sd[k] = (10.0 ** (torch.rand(sd[k].shape, generator=g) * 2.0 - 1.5)).to(torch.float32)
+        elif k.endswith("attn.proj.weight") or k.endswith("mlp.fc2.weight"):
+            w = sd[k]
+            chi2 = (torch.randn((3, w.shape[0]), generator=g) ** 2).sum(0)
+            t = torch.randn(w.shape, generator=g) / torch.sqrt(chi2[:, None] / 3.0)
+            sd[k] = (t / math.sqrt(w.shape[1]) * 0.7).to(torch.float32)
+    if pre + "register_tokens" in sd:
+        sd[pre + "register_tokens"] *= 8.0
+    return sd
+
+
 # ---- synthetic slices / volumes (SURVEY.md §8d) ---------------------------------------------------------------
 def _smooth_field(size, seed, n_blobs=12):
     rng = np.random.RandomState(seed)
