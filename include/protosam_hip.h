@@ -344,6 +344,18 @@ int psam_mask_stats(const float* low, int B, int C, int first, int nsel, int IN,
  * label uint8 [H,W]: counts int64 [n,3] = {tp, fp, fn} against it (models/SamWrapper.py:8-13 get_iou). */
 int psam_mask_binarize(const float* low, const int* idx, int n, int IN, int MID, int H, int W, int variant, float thr,
                        unsigned char* out, const unsigned char* label, long long* counts, void* stream);
+/* psam_mask_binarize's {tp, fp, fn} for rows chosen on the device, without the masks: row i's plane (into low viewed as
+ * [planes,IN,IN]) is rows[i * row_stride] - the plane field of a psam_amg_select record - and the number of rows is *count (device
+ * memory) clamped to max_rows; rows beyond it, and rows whose plane is outside [0, planes), do nothing. counts int64 [max_rows,3],
+ * zeroed here for all max_rows. Nothing returns to the host. max_rows <= 65535. models/SamWrapper.py:8-13 */
+int psam_mask_counts(const float* low, int planes, const int* rows, int row_stride, const int* count, int max_rows, int IN, int MID,
+                     int H, int W, int variant, float thr, const unsigned char* label, long long* counts, void* stream);
+/* The row the loop of models/SamWrapper.py:40-46 picks from counts int64 [.,3] over the first min(*count, max_rows) rows: IoU =
+ * tp / (tp + fp + fn) in float64, row 0 is taken whatever its IoU (NaN included: nothing beats NaN), a later row wins only with
+ * `>`. best int32 [4] = {plane of the winner = rows[row * row_stride], its row, 1 if there is no row (then plane 0, row -1),
+ * rows looked at}; *iou = the winner's IoU (NaN if there is no row). One wave. */
+int psam_best_iou(const long long* counts, const int* rows, int row_stride, const int* count, int max_rows, int* best, double* iou,
+                  void* stream);
 /* the same statistics (and the binary masks, out uint8 [n,H,W] or null) of MATERIALISED candidate planes fp32 [n,H,W]: the
  * generator's crop layers / images not at the model input size (second resize of postprocess_masks).
  * automatic_mask_generator.py:221-316; utils/amg.py:156-176, 303-346 */
@@ -420,6 +432,34 @@ int psam_topk_points_batch(const int* labels, const float* pfg, long long pfg_st
  * keys uint64 [R][k]. */
 int psam_topk_points(const int* labels, const float* pfg, const double* tab, int cap, int H, int W, int k, int max_comp,
                      int only_best, unsigned long long* keys, void* scratch, long long scratch_bytes, void* stream);
+
+/* Box NMS and the automatic mask generator's candidate selection on the device (csrc/nms.hip), bit for bit the host code of
+ * segment_anything/utils/amg.py nms_xyxy (the contract of torchvision's batched_nms, automatic_mask_generator.py:262-268) and of
+ * the score filters in front of it (automatic_mask_generator.py:293-303). Rows come in G groups: group g is rows offsets[g] ..
+ * offsets[g+1] (int32 [G+1] in DEVICE memory, ascending, within [0, n]); max_group >= the largest group, 1 <= max_group <= 16384
+ * (a 64 x 64 point grid gives 12288 candidates). A group whose offsets break these rules gets count[g] = -1 and nothing else.
+ * psam_nms_workspace: bytes of scratch for G groups of up to max_group rows; host arithmetic only.
+ * psam_box_nms: boxes [n,4] (x0, y0, x1, y1) int32, or fp32 with boxes_fp32; scores fp32 [n]; both finite, boxes 16-byte aligned.
+ *   Rows are visited by decreasing score, equal scores in index order (-0.0 == 0.0); a visited row is kept and removes every later
+ *   row whose IoU with it, widened to double, is > thr (== thr stays; 0 / 0 of two empty boxes is NaN and removes nothing); a
+ *   removed row removes nothing. Areas, intersection, union and the correctly rounded quotient are separately rounded fp32
+ *   operations. kept int32 [G,cap]: group g's kept rows (indices inside the group) in visiting order; count int32 [G]: how many
+ *   were kept - which may exceed cap: only the first cap are stored, the rest of a kept row is not written.
+ * psam_amg_select: stats int32 [n,8] as psam_mask_stats writes it; iou4 fp32 [(n+2)/3, 4], the decoder's predicted IoUs read in
+ *   place: candidate c is row c / 3, column 1 + c % 3. A candidate passes if iou > (float)pred_iou_thresh (applied only when
+ *   pred_iou_thresh > 0) and (float)stats[0] / (float)stats[1] >= (float)stability_thresh (only when > 0; 0 / 0 fails); its box is
+ *   stats[3..6], or [0,0,0,0] where stats[2] == 0; its score is the predicted IoU. records int32 [G,cap,9], per kept candidate in
+ *   visiting order {c, plane (c / 3) * 4 + 1 + c % 3 of the decoder's [.,4,256,256] output viewed as planes, predicted IoU bits,
+ *   stability bits (a NaN, 0 / 0 with the filter off, as 0x7fc00000), area, x0, y0, x1, y1}; count as above. One copy of records and count gives the host every field of a record.
+ * Status 1 before any launch: G < 1 or > 65535, max_group outside 1 .. 16384, n < 0, cap < 1, a NaN threshold, a null or
+ * misaligned (16 bytes) pointer, scratch too small. Stream-ordered launches only, no flags or waits between workgroups; every
+ * loop is bounded by the group's size. */
+int psam_nms_workspace(int G, int max_group, long long* bytes);
+int psam_box_nms(const void* boxes, int boxes_fp32, const float* scores, const int* offsets, int n, int G, int max_group,
+                 double thr, int* kept, int cap, int* count, void* scratch, long long scratch_bytes, void* stream);
+int psam_amg_select(const int* stats, const float* iou4, const int* offsets, int n, int G, int max_group, double pred_iou_thresh,
+                    double stability_thresh, double nms_thresh, int* records, int cap, int* count, void* scratch,
+                    long long scratch_bytes, void* stream);
 
 /* Slice hand-off from a scan volume (raw NIfTI voxels [Z,H,W]; vol_dtype 0 int16, 1 float32, 2 uint8, 3 int32).
  * psam_volume_stats: out[0] = sum(x), out[1] = sum(x^2) in fp64, x = voxel*slope + inter  (MR_normalize / get_CT_statistics,

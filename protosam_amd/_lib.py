@@ -92,6 +92,13 @@ SIGNATURES = {
     "psam_topk_points_workspace": [c_int, c_int, c_int, ctypes.POINTER(c_longlong)],
     "psam_topk_points_batch": [c_void_p, c_void_p, c_longlong, c_void_p] + [c_int] * 7 + [c_void_p, c_void_p, c_longlong, c_void_p],
     "psam_topk_points": [c_void_p, c_void_p, c_void_p] + [c_int] * 6 + [c_void_p, c_void_p, c_longlong, c_void_p],
+    "psam_nms_workspace": [c_int, c_int, ctypes.POINTER(c_longlong)],
+    "psam_box_nms": [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, ctypes.c_double, c_void_p, c_int, c_void_p, c_void_p,
+                     c_longlong, c_void_p],
+    "psam_amg_select": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                        c_void_p, c_int, c_void_p, c_void_p, c_longlong, c_void_p],
+    "psam_mask_counts": [c_void_p, c_int, c_void_p, c_int, c_void_p] + [c_int] * 6 + [c_float, c_void_p, c_void_p, c_void_p],
+    "psam_best_iou": [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p],
     "psam_mask_downscale": [c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p],
     "psam_plane_stats": [c_void_p, c_int, c_int, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p],
     "psam_rle_workspace": [c_int, c_int, ctypes.POINTER(c_longlong)],

@@ -1356,6 +1356,103 @@ extern "C" int psam_mask_binarize(const float* low, const int* idx, int n, int I
   return psam_launch_status();
 }
 
+// mask_binarize_kernel without the masks, for rows that are chosen on the device: row i's plane is rows[i * row_stride] (the plane
+// field of a psam_amg_select record), the number of rows is *count clamped to max_rows, and a row beyond it does nothing.
+// counts[i] = {tp, fp, fn} against the label; zeroed for all max_rows by the launcher.
+__global__ __launch_bounds__(256) void mask_counts_kernel(const float* __restrict__ low, const int* __restrict__ rows, int row_stride,
+                                                          const int* __restrict__ count, int planes, int IN, int MID, int H, int W,
+                                                          int variant, float thr, const uint8_t* __restrict__ label,
+                                                          unsigned long long* __restrict__ counts) {
+  const int i = blockIdx.y;
+  if (i >= *count) return;
+  const int pl = rows[(size_t)i * row_stride];
+  if (pl < 0 || pl >= planes) return;
+  const float* src = low + (size_t)pl * IN * IN;
+  const int y0 = blockIdx.x * MS_ROWS, y1 = min(y0 + MS_ROWS, H);
+  int tp = 0, fp = 0, fn = 0;
+  for (int y = y0; y < y1; ++y) {
+    for (int x = threadIdx.x; x < W; x += blockDim.x) {
+      const int m = up_sample(src, IN, MID, y, x, variant) > thr;
+      const int l = label[(size_t)y * W + x] != 0;
+      tp += m & l; fp += m & (!l); fn += (!m) & l;
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    tp += __shfl_xor(tp, o, 64); fp += __shfl_xor(fp, o, 64); fn += __shfl_xor(fn, o, 64);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    if (tp) atomicAdd(counts + (size_t)i * 3 + 0, (unsigned long long)tp);
+    if (fp) atomicAdd(counts + (size_t)i * 3 + 1, (unsigned long long)fp);
+    if (fn) atomicAdd(counts + (size_t)i * 3 + 2, (unsigned long long)fn);
+  }
+}
+extern "C" int psam_mask_counts(const float* low, int planes, const int* rows, int row_stride, const int* count, int max_rows, int IN,
+                                int MID, int H, int W, int variant, float thr, const uint8_t* label, long long* counts,
+                                void* stream) {
+  if (planes <= 0 || max_rows <= 0 || max_rows > 65535 || row_stride < 1 || IN <= 0 || variant < 0 || variant > 2 || H <= 0 ||
+      W <= 0 || H > MID || W > MID || !low || !rows || !count || !label || !counts)
+    return PSAM_ERR_ARG;
+  (void)hipMemsetAsync(counts, 0, sizeof(long long) * 3 * max_rows, (hipStream_t)stream);
+  hipLaunchKernelGGL(mask_counts_kernel, dim3((H + MS_ROWS - 1) / MS_ROWS, max_rows), dim3(256), 0, (hipStream_t)stream, low, rows,
+                     row_stride, count, planes, IN, MID, H, W, variant, thr, label, (unsigned long long*)counts);
+  return psam_launch_status();
+}
+
+// The row SamWrapper.forward's loop picks (models/SamWrapper.py:40-46): IoU = tp / (tp + fp + fn) in float64; row 0 is taken
+// whatever its IoU (NaN included, and then nothing beats it: v > NaN is false); a later row wins only with `>`. One wave: lane l
+// scans rows l, l + 64, ... in ascending order, then the lanes' candidates are merged (larger IoU, lower row among equals).
+// best = {plane of the winner, its row, 1 if the group is empty (then plane 0, row -1), rows scanned}; *iou its IoU (NaN if empty).
+__global__ __launch_bounds__(64) void best_iou_kernel(const long long* __restrict__ counts, const int* __restrict__ rows,
+                                                      int row_stride, const int* __restrict__ count, int max_rows,
+                                                      int* __restrict__ best, double* __restrict__ iou) {
+  const int lane = threadIdx.x;
+  int n = *count;
+  n = n < 0 ? 0 : (n < max_rows ? n : max_rows);
+  if (n == 0) {
+    if (lane == 0) {
+      best[0] = 0; best[1] = -1; best[2] = 1; best[3] = 0;
+      *iou = __longlong_as_double(0x7ff8000000000000LL);
+    }
+    return;
+  }
+  const double tp0 = (double)counts[0], v0 = tp0 / (tp0 + (double)counts[1] + (double)counts[2]);
+  int bi = 0x7fffffff;
+  double bv = 0.0;
+  if (v0 == v0) {
+    for (int i = lane; i < n; i += 64) {
+      const double tp = (double)counts[(size_t)i * 3];
+      const double v = tp / (tp + (double)counts[(size_t)i * 3 + 1] + (double)counts[(size_t)i * 3 + 2]);
+      if (v == v && (bi == 0x7fffffff || v > bv)) {
+        bi = i;
+        bv = v;
+      }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const int oi = __shfl_xor(bi, o, 64);
+      const double ov = __shfl_xor(bv, o, 64);
+      if (oi != 0x7fffffff && (bi == 0x7fffffff || ov > bv || (ov == bv && oi < bi))) {
+        bi = oi;
+        bv = ov;
+      }
+    }
+  } else {
+    bi = 0;
+    bv = v0;
+  }
+  if (lane == 0) {
+    best[0] = rows[(size_t)bi * row_stride]; best[1] = bi; best[2] = 0; best[3] = n;
+    *iou = bv;
+  }
+}
+extern "C" int psam_best_iou(const long long* counts, const int* rows, int row_stride, const int* count, int max_rows, int* best,
+                             double* iou, void* stream) {
+  if (max_rows <= 0 || row_stride < 1 || !counts || !rows || !count || !best || !iou) return PSAM_ERR_ARG;
+  hipLaunchKernelGGL(best_iou_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, counts, rows, row_stride, count, max_rows, best, iou);
+  return psam_launch_status();
+}
+
 // Statistics (and the binary mask) of MATERIALISED candidate planes: the crop layers of the automatic mask generator
 // (automatic_mask_generator.py:221-316 with crop_n_layers > 0) and images that are not at the model's input size take the second
 // resize of postprocess_masks, so their candidates exist at full resolution before they are reduced. planes fp32 [n, H, W]

@@ -101,6 +101,13 @@ def _req(t, dtype, name):
         raise ValueError(f"{name}: innermost dimension must be contiguous")
 
 
+def _req_rows(t, dtype, name):
+    """_req for a table that may have no rows (an empty tensor's strides say nothing, so only device and dtype are asked)"""
+    if t is not None and t.is_cuda and t.dtype == dtype and t.numel() == 0:
+        return
+    _req(t, dtype, name)
+
+
 def _req_aligned(t, nbytes, name):
     """The kernel behind reads or writes `t` in `nbytes` pieces from its base pointer: a view that starts inside a storage, off
     that boundary, is refused here, on the host, before any call into the library."""
@@ -1211,6 +1218,162 @@ def mask_binarize(low, idx, MID, H, W, variant, thr=0.0, label=None, out=None):
                                       _ptr(label), _ptr(counts), _stream())
     _lib.check(st, "psam_mask_binarize")
     return out, counts
+
+
+NMS_MAX_GROUP = 16384   # candidates psam_box_nms / psam_amg_select take per group (csrc/nms.hip)
+AMG_REC = 9             # int32 words of a psam_amg_select record: candidate, plane, IoU bits, stability bits, area, x0, y0, x1, y1
+_nms_scratch = {}
+_nms_offsets = {}
+
+
+def nms_workspace(G, max_group):
+    """Bytes of scratch psam_box_nms / psam_amg_select need for G groups of up to max_group rows (psam_nms_workspace)."""
+    nbytes = _lib.c_longlong(0)
+    _lib.check(_lib.lib().psam_nms_workspace(G, max_group, nbytes), "psam_nms_workspace")
+    return nbytes.value
+
+
+def _nms_groups(offsets, n, device):
+    """Host-side check of the group offsets (a sequence of G + 1 ascending ints from 0 to n, no group above NMS_MAX_GROUP) ->
+    (device int32 copy, cached per value, G, largest group or 1)."""
+    off = tuple(int(v) for v in offsets)
+    if len(off) < 2 or off[0] != 0 or off[-1] != n or any(b < a for a, b in zip(off, off[1:])):
+        raise ValueError(f"offsets must ascend from 0 to {n} over at least one group, got {off[:8]}{'...' if len(off) > 8 else ''}")
+    big = max(b - a for a, b in zip(off, off[1:]))
+    if big > NMS_MAX_GROUP:
+        raise ValueError(f"a group of {big} candidates exceeds the capacity of {NMS_MAX_GROUP}")
+    key = (str(device), off)
+    if key not in _nms_offsets:
+        if len(_nms_offsets) > 64:
+            _nms_offsets.clear()
+        _nms_offsets[key] = torch.tensor(off, dtype=torch.int32).to(device)
+    return _nms_offsets[key], len(off) - 1, max(big, 1)
+
+
+def _nms_scratch_for(G, maxg, device, scratch):
+    if scratch is None:
+        key = (str(device), G, maxg)
+        if key not in _nms_scratch:
+            _nms_scratch[key] = torch.empty((nms_workspace(G, maxg) + 7) // 8, dtype=torch.int64, device=device)
+        scratch = _nms_scratch[key]
+    if not scratch.is_cuda or scratch.dtype != torch.int64 or not scratch.is_contiguous():
+        raise TypeError("scratch: expected a contiguous int64 device tensor")
+    _req_aligned(scratch, 16, "scratch")
+    return scratch
+
+
+def box_nms(boxes, scores, offsets, iou_threshold, cap=None, kept=None, count=None, scratch=None):
+    """Box NMS per group on the device (psam_box_nms), equal to utils.amg.nms_xyxy on every group: boxes int32 or fp32 [n,4] (x0,
+    y0, x1, y1), scores fp32 [n], `offsets` a HOST sequence of G + 1 ascending ints (group g = rows offsets[g]:offsets[g+1], at most
+    NMS_MAX_GROUP each) -> (kept int32 [G,cap]: indices inside the group in suppression order, count int32 [G]: the number kept,
+    which may exceed cap - then only the first cap are stored). cap defaults to the largest group. `scratch`: int64 tensor of
+    nms_workspace bytes (default: cached per shape); calls on one stream share it in order."""
+    if boxes is None or scores is None or not torch.is_tensor(boxes) or not torch.is_tensor(scores):
+        raise TypeError("boxes, scores: expected tensors")
+    if boxes.dtype not in (torch.int32, torch.float32):
+        raise TypeError(f"boxes: expected torch.int32 or torch.float32, got {boxes.dtype}")
+    _req_rows(boxes, boxes.dtype, "boxes"); _req_rows(scores, torch.float32, "scores")
+    if boxes.dim() != 2 or boxes.shape[1] != 4 or not boxes.is_contiguous() or not scores.is_contiguous():
+        raise ValueError(f"boxes: expected a contiguous [n, 4], got {tuple(boxes.shape)}")
+    n = boxes.shape[0]
+    if scores.numel() != n:
+        raise ValueError(f"scores: expected {n} values, got {scores.numel()}")
+    _req_aligned(boxes, 16, "boxes")
+    off_d, G, maxg = _nms_groups(offsets, n, boxes.device)
+    cap = maxg if cap is None else int(cap)
+    if cap < 1:
+        raise ValueError(f"cap must be at least 1, got {cap}")
+    if kept is None:
+        kept = torch.empty((G, cap), dtype=torch.int32, device=boxes.device)
+    if count is None:
+        count = torch.empty((G,), dtype=torch.int32, device=boxes.device)
+    _req(kept, torch.int32, "kept"); _req(count, torch.int32, "count")
+    assert kept.is_contiguous() and kept.numel() >= G * cap and count.is_contiguous() and count.numel() >= G
+    scratch = _nms_scratch_for(G, maxg, boxes.device, scratch)
+    st = _lib.lib().psam_box_nms(_ptr(boxes), 1 if boxes.dtype == torch.float32 else 0, _ptr(scores), _ptr(off_d), n, G, maxg,
+                                 float(iou_threshold), _ptr(kept), cap, _ptr(count), _ptr(scratch), scratch.numel() * 8, _stream())
+    _lib.check(st, "psam_box_nms")
+    return kept, count
+
+
+def amg_select(stats, iou4, offsets, pred_iou_thresh, stability_score_thresh, box_nms_thresh, cap=None, out=None, scratch=None):
+    """The generator's score filters and box NMS on the device (psam_amg_select), equal to automatic_mask_generator.py's host lines:
+    stats int32 [n,8] (mask_stats), iou4 fp32 [ceil(n/3),4] (the decoder's IoU output, candidate c = row c // 3, column 1 + c % 3),
+    `offsets` as box_nms. -> (records int32 [G,cap,AMG_REC], count int32 [G]), both views of ONE int32 tensor `out` of G * cap *
+    AMG_REC + G words (records first), so that one copy brings everything to the host. A filter threshold <= 0 switches that filter
+    off. count may exceed cap (default: the largest group): only the first cap records are stored."""
+    _req_rows(stats, torch.int32, "stats"); _req_rows(iou4, torch.float32, "iou4")
+    if stats is None or iou4 is None:
+        raise TypeError("stats, iou4: expected tensors")
+    if stats.dim() != 2 or stats.shape[1] != 8 or not stats.is_contiguous():
+        raise ValueError(f"stats: expected a contiguous [n, 8], got {tuple(stats.shape)}")
+    n = stats.shape[0]
+    if iou4.dim() != 2 or iou4.shape[1] != 4 or not iou4.is_contiguous() or iou4.shape[0] * 3 < n:
+        raise ValueError(f"iou4: expected a contiguous [>= {(n + 2) // 3}, 4], got {tuple(iou4.shape)}")
+    off_d, G, maxg = _nms_groups(offsets, n, stats.device)
+    cap = maxg if cap is None else int(cap)
+    if cap < 1:
+        raise ValueError(f"cap must be at least 1, got {cap}")
+    words = G * cap * AMG_REC + G
+    if out is None:
+        out = torch.empty((words,), dtype=torch.int32, device=stats.device)
+    _req(out, torch.int32, "out")
+    assert out.is_contiguous() and out.numel() >= words
+    records, count = out[:G * cap * AMG_REC].view(G, cap, AMG_REC), out[G * cap * AMG_REC:words]
+    scratch = _nms_scratch_for(G, maxg, stats.device, scratch)
+    st = _lib.lib().psam_amg_select(_ptr(stats), _ptr(iou4), _ptr(off_d), n, G, maxg, float(pred_iou_thresh),
+                                    float(stability_score_thresh), float(box_nms_thresh), _ptr(records), cap, _ptr(count),
+                                    _ptr(scratch), scratch.numel() * 8, _stream())
+    _lib.check(st, "psam_amg_select")
+    return records, count
+
+
+def mask_counts(low, records, count, MID, H, W, variant, label, thr=0.0, counts=None):
+    """int64 [cap,3] {tp, fp, fn} against `label` uint8 [H,W] of the first min(count, cap) records of ONE group (records int32
+    [cap,AMG_REC], count int32 [1], both on the device, as amg_select leaves them): mask_binarize's counts without the masks and
+    without the host knowing how many rows there are. Rows beyond the count stay zero."""
+    _req(low, torch.float32, "low"); _req(records, torch.int32, "records"); _req(count, torch.int32, "count")
+    _req(label, torch.uint8, "label")
+    if low is None or records is None or count is None or label is None:
+        raise TypeError("low, records, count, label: expected tensors")
+    if records.dim() != 2 or records.shape[1] != AMG_REC or not records.is_contiguous() or count.numel() != 1:
+        raise ValueError(f"records / count: expected one group [cap, {AMG_REC}] and [1], got {tuple(records.shape)}, {tuple(count.shape)}")
+    cap = records.shape[0]
+    if cap < 1 or cap > 65535:
+        raise ValueError(f"records: 1 .. 65535 rows, got {cap}")
+    assert low.is_contiguous() and label.is_contiguous() and tuple(label.shape) == (H, W)
+    IN = low.shape[-1]
+    if counts is None:
+        counts = torch.empty((cap, 3), dtype=torch.int64, device=low.device)
+    _req(counts, torch.int64, "counts")
+    assert counts.is_contiguous() and counts.numel() >= cap * 3
+    st = _lib.lib().psam_mask_counts(_ptr(low), low.numel() // (IN * IN), _ptr(records[:, 1:]), AMG_REC, _ptr(count), cap, IN, MID, H,
+                                     W, variant, float(thr), _ptr(label), _ptr(counts), _stream())
+    _lib.check(st, "psam_mask_counts")
+    return counts
+
+
+def best_iou(counts, records, count, best=None, iou=None):
+    """The row SamWrapper.forward's loop picks among the first min(count, cap) rows of counts int64 [cap,3] (psam_best_iou): IoU =
+    tp / (tp + fp + fn) in float64, row 0 whatever its IoU, a later row only with `>`. -> (best int32 [4] = {plane of the winner
+    (records[row, 1]), its row, 1 if there is no row (then plane 0, row -1), rows looked at}, iou float64 [1]), on the device."""
+    _req(counts, torch.int64, "counts"); _req(records, torch.int32, "records"); _req(count, torch.int32, "count")
+    if counts is None or records is None or count is None:
+        raise TypeError("counts, records, count: expected tensors")
+    if records.dim() != 2 or records.shape[1] != AMG_REC or not records.is_contiguous() or count.numel() != 1:
+        raise ValueError(f"records / count: expected one group [cap, {AMG_REC}] and [1], got {tuple(records.shape)}, {tuple(count.shape)}")
+    cap = records.shape[0]
+    if cap < 1 or counts.dim() != 2 or counts.shape[1] != 3 or counts.shape[0] < cap or not counts.is_contiguous():
+        raise ValueError(f"counts: expected a contiguous [>= {cap}, 3], got {tuple(counts.shape)}")
+    if best is None:
+        best = torch.empty((4,), dtype=torch.int32, device=counts.device)
+    if iou is None:
+        iou = torch.empty((1,), dtype=torch.float64, device=counts.device)
+    _req(best, torch.int32, "best"); _req(iou, torch.float64, "iou")
+    assert best.numel() >= 4 and iou.numel() >= 1
+    st = _lib.lib().psam_best_iou(_ptr(counts), _ptr(records[:, 1:]), AMG_REC, _ptr(count), cap, _ptr(best), _ptr(iou), _stream())
+    _lib.check(st, "psam_best_iou")
+    return best, iou
 
 
 def _rle_masks(masks):

@@ -51,13 +51,7 @@ class SamWrapper(nn.Module):
         uint8 (used by `SamWrapperWrapper`)."""
         image = self.transform.apply_image(image)                               # :37
         dev = self.sam.device
-        lab = torch.as_tensor(np.asarray(image_labels) if not torch.is_tensor(image_labels) else image_labels)
-        if lab.numel() and (int(lab.min()) < 0 or int(lab.max()) > 1):
-            raise ValueError("image_labels must be binary {0, 1} (models/ProtoSAM.py:124-125)")
-        if tuple(lab.shape) != tuple(image.shape[:2]):
-            raise ValueError(f"operands could not be broadcast together with shapes {tuple(image.shape[:2])} "
-                             f"{tuple(lab.shape)}")                            # numpy's error in get_iou, :8-10
-        lab = lab.to(device=dev, dtype=torch.uint8).contiguous()
+        lab = self._check_label(image, image_labels).to(device=dev, dtype=torch.uint8).contiguous()
         cand, masks, counts = self.mask_generator.generate_device(image, lab)   # :38
         if masks.shape[0] == 0:
             raise TypeError("list indices must be integers or slices, not NoneType")   # masks[None], :48
@@ -73,6 +67,84 @@ class SamWrapper(nn.Module):
         if return_device:
             return masks[best]
         return masks[best].cpu().numpy().astype(bool)
+
+    @staticmethod
+    def _check_label(image, image_labels):
+        """`forward`'s label checks -> the label as a tensor (on whatever device it came)."""
+        lab = torch.as_tensor(np.asarray(image_labels) if not torch.is_tensor(image_labels) else image_labels)
+        if lab.numel() and (int(lab.min()) < 0 or int(lab.max()) > 1):
+            raise ValueError("image_labels must be binary {0, 1} (models/ProtoSAM.py:124-125)")
+        if tuple(lab.shape) != tuple(image.shape[:2]):
+            raise ValueError(f"operands could not be broadcast together with shapes {tuple(image.shape[:2])} "
+                             f"{tuple(lab.shape)}")                            # numpy's error in get_iou, :8-10
+        return lab
+
+    @torch.no_grad()
+    def forward_batch(self, images, labels, return_device=False):
+        """`forward` for B images of one size in one call: -> bool numpy [B, H, W] (uint8 on the device with `return_device`),
+        equal to `forward(images[b], labels[b])` mask for mask. Labels are validated up front with `forward`'s messages. Per image
+        one chain is enqueued with nothing read back - encode, decode, statistics, `psam_amg_select` (filters + box NMS),
+        `psam_mask_counts` ({tp, fp, fn} of the survivors), `psam_best_iou`, and the binarisation of the one winning plane - and
+        the decoder's output buffer is reused in stream order. The host waits once, after the last image; an image without a
+        surviving proposal then raises `forward`'s TypeError. `last_stats` becomes a list with one `forward`-style dict per image.
+        A generator that is off the fused path (crop layers, small-region removal) runs `forward` image by image."""
+        from . import ops
+        raw = list(images)
+        images = [self.transform.apply_image(im) for im in raw]                 # :37
+        labels = list(labels)
+        if len(labels) != len(images):
+            raise ValueError(f"{len(images)} images but {len(labels)} labels")
+        if len(images) == 0:
+            raise ValueError("forward_batch needs at least one image")
+        dev = self.sam.device
+        labs = [self._check_label(im, lb) for im, lb in zip(images, labels)]
+        if any(im.shape[:2] != images[0].shape[:2] for im in images):
+            raise ValueError("forward_batch: all images of a batch must have the same size")
+        g = self.mask_generator
+        if not all(g._fast_path(im) for im in images):
+            outs, stats = [], []
+            for im, lb in zip(raw, labs):
+                outs.append(self.forward(im, lb, return_device=return_device))
+                stats.append(self.last_stats)
+            self.last_stats = stats
+            return torch.stack(outs) if return_device else np.stack(outs)
+        B = len(images)
+        h, w = images[0].shape[:2]
+        sam = self.sam
+        labs = [lb.to(device=dev, dtype=torch.uint8).contiguous() for lb in labs]
+        masks = torch.empty((B, h, w), dtype=torch.uint8, device=dev)
+        best = torch.empty((B, 4), dtype=torch.int32, device=dev)
+        best_iou = torch.empty((B,), dtype=torch.float64, device=dev)
+        tables, counts, ctxs = None, None, []
+        for b, im in enumerate(images):
+            ctx = g._enqueue(im)
+            if tables is None:
+                cap = 3 * ctx["n"]
+                tables = torch.empty((B, cap * ops.AMG_REC + 1), dtype=torch.int32, device=dev)
+                counts = torch.empty((B, cap, 3), dtype=torch.int64, device=dev)
+            _, records, count = g._select_enqueue(ctx, out=tables[b])
+            ops.mask_counts(ctx["low"], records, count, sam.image_encoder.img_size, h, w, sam.variant_id(), labs[b],
+                            float(sam.mask_threshold), counts=counts[b])
+            ops.best_iou(counts[b], records, count, best=best[b], iou=best_iou[b:b + 1])
+            ops.mask_binarize(ctx["low"], best[b, :1], sam.image_encoder.img_size, h, w, sam.variant_id(),
+                              float(sam.mask_threshold), out=masks[b:b + 1])
+            ctxs.append(dict(pts=ctx["pts"], size=ctx["size"], n=ctx["n"]))
+        best_h = best.cpu().numpy()                                             # the batch's one wait
+        iou_h, tab_h, cnt_h = best_iou.cpu().numpy(), tables.cpu().numpy(), counts.cpu().numpy()
+        stats = []
+        for b in range(B):
+            if best_h[b, 2]:
+                raise TypeError("list indices must be integers or slices, not NoneType")   # masks[None], :48
+            k = int(best_h[b, 3])
+            c = cnt_h[b, :k].astype(np.float64)
+            with np.errstate(divide="ignore", invalid="ignore"):
+                ious = c[:, 0] / (c[:, 0] + c[:, 1] + c[:, 2])
+            cand = g._cand_from_records(ctxs[b], tab_h[b], tables[b, :cap * ops.AMG_REC].view(cap, ops.AMG_REC))
+            stats.append(dict(n_masks=k, best_index=int(best_h[b, 1]), best_iou=float(iou_h[b]), ious=ious, candidates=cand))
+        self.last_stats = stats
+        if return_device:
+            return masks
+        return masks.cpu().numpy().astype(bool)
 
     def to(self, device):
         self.sam.to(device)

@@ -28,6 +28,8 @@ without it (:116-117); with it, the segmentation is `coco_encode_rle` of the unc
 project's own restatement of the COCO string form. Without the package, `coco_encode_rle(rec["segmentation"])` on the
 records of output_mode "uncompressed_rle" gives the same COCO record.
 """
+import os
+
 import numpy as np
 import torch
 
@@ -67,6 +69,11 @@ class SamAutomaticMaskGenerator:
         self.output_mode = output_mode
         self.custom_points = custom_points
         self.decode_chunk = decode_chunk
+        # where the fused path filters and suppresses its candidates: "host" (numpy + nms_xyxy between two device stages, the
+        # default) or "device" (psam_amg_select); the batch entry points always select on the device
+        self.amg_select = os.environ.get("PSAM_AMG_SELECT", "host")
+        if self.amg_select not in ("host", "device"):
+            raise ValueError(f"PSAM_AMG_SELECT must be 'host' or 'device', got {self.amg_select!r}")
         self._low = None
 
     def to(self, device):  # models/SamWrapper.py:52-54 calls this
@@ -86,10 +93,21 @@ class SamAutomaticMaskGenerator:
             out[lo + m // 2: lo + m] = 0
         return out
 
+    def _buffers(self, n, dev, slot=0):
+        """The decoder's outputs for n prompts: (low [n,4,256,256], iou [n,4]) fp32 on the device. Slot 0 is `self._low` /
+        `self._iou`, what the single-image entry points use; slot 1 is the second pair `generate_batch` alternates with."""
+        names = ("_low", "_iou") if slot == 0 else ("_low_b", "_iou_b")
+        low = getattr(self, names[0], None)
+        if low is None or low.shape[0] != n or low.device != dev:
+            setattr(self, names[0], torch.empty((n, 4, 256, 256), dtype=torch.float32, device=dev))
+            setattr(self, names[1], torch.empty((n, 4), dtype=torch.float32, device=dev))
+        return getattr(self, names[0]), getattr(self, names[1])
+
     @torch.no_grad()
-    def _candidates(self, image):
-        """Layer-0 crop (the whole image): encode, decode every grid point, reduce, filter, NMS.
-        -> dict of numpy arrays over the kept candidates (NMS order) + `plane` (int32 device indices into self._low)."""
+    def _enqueue(self, image, slot=0):
+        """Layer-0 crop (the whole image): encode, decode every grid point, reduce. Everything is enqueued, nothing is read back.
+        -> dict(pts, size, n, low, iou, stats): the grid points (host), the decoder's outputs and the int32 [3n, 8] statistics
+        table (device)."""
         pr = self.predictor
         sam = pr.model
         h, w = image.shape[:2]
@@ -107,21 +125,24 @@ class SamAutomaticMaskGenerator:
         dpk = sam.mask_decoder._packed()
         coords_d = torch.from_numpy(coords).to(dev)
         lab_d = torch.from_numpy(np.ascontiguousarray(lab2)).to(dev)
-        if self._low is None or self._low.shape[0] != n or self._low.device != dev:
-            self._low = torch.empty((n, 4, 256, 256), dtype=torch.float32, device=dev)
-            self._iou = torch.empty((n, 4), dtype=torch.float32, device=dev)
+        low, iou = self._buffers(n, dev, slot)
         feat_tok = pr.features_tokens[0]
         for lo in range(0, n, self.decode_chunk):                               # :255-259 / predictor.py:216-235
             hi = min(lo + self.decode_chunk, n)
             tokens = ops.prompt_tokens(coords_d[lo:hi], lab_d[lo:hi], pe["G"], pe["type_emb"], dpk["out_tok"], hi - lo, 2,
                                        float(S))
             sam.mask_decoder.predict_masks_tokens(feat_tok, pe["pe_tok"], tokens, pe["no_mask"],
-                                                  masks_out=self._low[lo:hi], iou_out=self._iou[lo:hi])
+                                                  masks_out=low[lo:hi], iou_out=iou[lo:hi])
         pr.reset_image()                                                        # :260
         thr = float(sam.mask_threshold)
-        stats = ops.mask_stats(self._low, 1, 3, S, h, w, sam.variant_id(), thr, self.stability_score_offset)
-        stats = stats.cpu().numpy()
-        iou = self._iou[:, 1:].reshape(-1).cpu().numpy()                        # multimask_output=True, flatten(0, 1)
+        stats = ops.mask_stats(low, 1, 3, S, h, w, sam.variant_id(), thr, self.stability_score_offset)
+        return dict(pts=pts, size=(h, w), n=n, low=low, iou=iou, stats=stats)
+
+    def _select_host(self, ctx):
+        """The score filters and box NMS on the host: two downloads, numpy, one upload (the default, PSAM_AMG_SELECT=host)."""
+        pts, n, dev = ctx["pts"], ctx["n"], ctx["low"].device
+        stats = ctx["stats"].cpu().numpy()
+        iou = ctx["iou"][:, 1:].reshape(-1).cpu().numpy()                       # multimask_output=True, flatten(0, 1)
         keep = np.arange(3 * n)
         if self.pred_iou_thresh > 0.0:                                          # :293-295
             keep = keep[iou[keep] > self.pred_iou_thresh]
@@ -133,17 +154,53 @@ class SamAutomaticMaskGenerator:
         boxes[stats[:, 2] == 0] = 0                                             # empty mask -> [0,0,0,0] (amg.py:339-341)
         # is_box_near_crop_edge (:309-311) is vacuous for the layer-0 crop: the crop box IS the image box
         kept = keep[nms_xyxy(boxes[keep], iou[keep], self.box_nms_thresh)]      # :262-268
-        plane = (kept // 3) * 4 + 1 + kept % 3                                  # index into self._low.view(-1,256,256)
+        plane = (kept // 3) * 4 + 1 + kept % 3                                  # index into low.view(-1,256,256)
         return dict(iou_preds=iou[kept], stability_score=stab[kept], boxes=boxes[kept], area=stats[kept, 2],
-                    points=pts[kept // 3], plane=torch.from_numpy(plane.astype(np.int32)).to(dev), size=(h, w))
+                    points=pts[kept // 3], plane=torch.from_numpy(plane.astype(np.int32)).to(dev), size=ctx["size"])
 
-    def _binarize(self, cand, label=None):
+    def _select_enqueue(self, ctx, out=None):
+        """The same selection on the device (`psam_amg_select`), enqueued behind the statistics: -> (out, records int32 [3n,9],
+        count int32 [1]): `out` (given, or a new one) is the int32 device tensor of 3n * 9 + 1 words that holds the records and
+        then the count, so one copy of it brings the whole selection to the host."""
+        cap = 3 * ctx["n"]
+        if out is None:
+            out = torch.empty((cap * ops.AMG_REC + 1,), dtype=torch.int32, device=ctx["low"].device)
+        records, count = ops.amg_select(ctx["stats"], ctx["iou"], (0, cap), self.pred_iou_thresh, self.stability_score_thresh,
+                                        self.box_nms_thresh, cap=cap, out=out)
+        return out, records[0], count
+
+    @staticmethod
+    def _cand_from_records(ctx, table, records_dev):
+        """The candidate dict of `_select_host` from the record table alone: `table` = the host copy (numpy int32) of the tensor
+        behind `records_dev` [3n, 9] (records, then the count)."""
+        cap = 3 * ctx["n"]
+        k = min(int(table[cap * ops.AMG_REC]), cap)
+        r = table[:cap * ops.AMG_REC].reshape(cap, ops.AMG_REC)[:k].copy()     # (the caller may reuse `table`)
+        kept = r[:, 0].astype(np.int64)
+        # the plane column as a dense tensor (a new one: `.contiguous()` hands a one-row view back with its stride of 9)
+        plane = torch.empty((k,), dtype=torch.int32, device=records_dev.device).copy_(records_dev[:k, 1])
+        return dict(iou_preds=np.ascontiguousarray(r[:, 2]).view(np.float32), stability_score=np.ascontiguousarray(r[:, 3]).view(np.float32),
+                    boxes=r[:, 5:9].astype(np.int64), area=np.ascontiguousarray(r[:, 4]), points=ctx["pts"][kept // 3],
+                    plane=plane, size=ctx["size"])
+
+    @torch.no_grad()
+    def _candidates(self, image):
+        """Layer-0 crop (the whole image): encode, decode every grid point, reduce, filter, NMS.
+        -> dict of numpy arrays over the kept candidates (NMS order) + `plane` (int32 device indices into self._low)."""
+        ctx = self._enqueue(image)
+        if self.amg_select == "host":
+            return self._select_host(ctx)
+        out, records, _ = self._select_enqueue(ctx)
+        return self._cand_from_records(ctx, out.cpu().numpy(), records)                 # the one copy
+
+    def _binarize(self, cand, label=None, low=None):
         """uint8 device masks [n, H, W] of the kept candidates (+ {tp, fp, fn} vs `label` uint8 [H, W] on the device)."""
         sam = self.predictor.model
+        low = self._low if low is None else low
         h, w = cand["size"]
         if cand["plane"].numel() == 0:
-            return torch.empty((0, h, w), dtype=torch.uint8, device=self._low.device), None
-        return ops.mask_binarize(self._low, cand["plane"], sam.image_encoder.img_size, h, w, sam.variant_id(),
+            return torch.empty((0, h, w), dtype=torch.uint8, device=low.device), None
+        return ops.mask_binarize(low, cand["plane"], sam.image_encoder.img_size, h, w, sam.variant_id(),
                                  float(sam.mask_threshold), label=label)
 
     # ---- general path: crop layers, any image size, small-region removal -----------------------------------------------------
@@ -357,6 +414,10 @@ class SamAutomaticMaskGenerator:
             return anns
         cand = self._candidates(image)
         masks, _ = self._binarize(cand)
+        return self._fused_records(cand, masks)
+
+    def _fused_records(self, cand, masks):
+        """The records of the fused path from its candidate dict and the kept candidates' uint8 device masks."""
         masks = self._segmentations(masks)
         h, w = cand["size"]
         anns = []
@@ -371,6 +432,77 @@ class SamAutomaticMaskGenerator:
                 "crop_box": [0, 0, w, h],
             })
         return anns
+
+    def _pipelined(self, images, finish, fallback):
+        """The fused path over several images with the host one image behind the device: image i's encode, decode, statistics and
+        selection (`psam_amg_select`) are enqueued into buffer pair i % 2, its record table is copied to pinned memory behind an
+        event, and the host waits for that event only after image i + 1 has been enqueued; then `finish(i, cand, low)` enqueues
+        what works on the survivors. Every image is encoded and decoded by the calls `generate` makes, so its logits are the same
+        bits. Images off the fused path go to `fallback(i)` one by one, after what is pending."""
+        out = [None] * len(images)
+        pending = None
+
+        def drain():
+            nonlocal pending
+            if pending is not None:
+                i, ctx, records, host, ev = pending
+                pending = None
+                ev.synchronize()
+                out[i] = finish(i, self._cand_from_records(ctx, host.numpy(), records), ctx["low"])
+
+        k = 0
+        for i, image in enumerate(images):
+            if not self._fast_path(image):
+                drain()
+                out[i] = fallback(i)
+                continue
+            ctx = self._enqueue(image, slot=k % 2)
+            dev_out, records, _ = self._select_enqueue(ctx, out=self._select_out(ctx, k % 2))
+            host = self._pinned(dev_out.numel(), k % 2)
+            host.copy_(dev_out, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record()
+            drain()                                                             # image i - 1, while image i runs
+            pending = (i, ctx, records, host, ev)
+            k += 1
+        drain()
+        return out
+
+    def _select_out(self, ctx, slot):
+        """the device tensor behind the records and count of buffer pair `slot`"""
+        bufs = self.__dict__.setdefault("_sel_out", {})
+        words = 3 * ctx["n"] * ops.AMG_REC + 1
+        t = bufs.get(slot)
+        if t is None or t.numel() != words or t.device != ctx["low"].device:
+            t = bufs[slot] = torch.empty((words,), dtype=torch.int32, device=ctx["low"].device)
+        return t
+
+    def _pinned(self, words, slot):
+        bufs = self.__dict__.setdefault("_sel_host", {})
+        t = bufs.get(slot)
+        if t is None or t.numel() != words:
+            t = bufs[slot] = torch.empty((words,), dtype=torch.int32, pin_memory=True)
+        return t
+
+    @torch.no_grad()
+    def generate_batch(self, images):
+        """`[generate(im) for im in images]`, the same records, with the candidate selection on the device and the host's wait
+        for image i behind the enqueue of image i + 1 (see `_pipelined`). Images that take the general path are handled by
+        `generate` one by one."""
+        images = list(images)
+        return self._pipelined(images, lambda i, cand, low: self._fused_records(cand, self._binarize(cand, low=low)[0]),
+                               lambda i: self.generate(images[i]))
+
+    @torch.no_grad()
+    def generate_device_batch(self, images, labels=None):
+        """`[generate_device(im, lab) for im, lab in zip(images, labels)]` in the same way: a list of (candidate dict, uint8 device
+        masks [n,H,W], int64 [n,3] {tp, fp, fn} or None). `labels`: None, or one uint8 device label (or None) per image."""
+        images = list(images)
+        labels = [None] * len(images) if labels is None else list(labels)
+        if len(labels) != len(images):
+            raise ValueError(f"{len(images)} images but {len(labels)} labels")
+        return self._pipelined(images, lambda i, cand, low: (cand,) + tuple(self._binarize(cand, labels[i], low=low)),
+                               lambda i: self.generate_device(images[i], labels[i]))
 
     @torch.no_grad()
     def generate_device(self, image, label=None):
