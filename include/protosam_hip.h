@@ -360,6 +360,32 @@ int psam_best_iou(const long long* counts, const int* rows, int row_stride, cons
  * generator's crop layers / images not at the model input size (second resize of postprocess_masks).
  * automatic_mask_generator.py:221-316; utils/amg.py:156-176, 303-346 */
 int psam_plane_stats(const float* planes, int n, int H, int W, float thr, float off, int* stats, void* out, void* stream);
+/* psam_mask_stats / psam_mask_binarize for an image that is NOT at the model's input size (or a crop): both resizes of
+ * Sam.postprocess_masks (modeling/sam.py:132-160 / :296-320) per output pixel, nothing written in between. The value at (y, x) of
+ * the OH x OW image is the second-stage interpolation - source size ih x iw = predictor.input_size, the un-padded corner of the
+ * MID x MID first-stage map, so its taps clamp at ih - 1 / iw - 1 - of the first-stage values IN -> MID; variant 0 / 1 / 2 =
+ * bilinear align_corners False / True / nearest in BOTH stages (psam_mask_upsample's variants, psam_resize2d's modes), 3 is
+ * refused. Bit for bit the values of psam_mask_upsample -> [..., :ih, :iw] -> psam_resize2d (csrc/amg_resize.hip).
+ * psam_mask_stats_resized: low fp32 [B,C,IN,IN], plane p = prompt p / nsel, channel first + p % nsel -> stats int32 [B*nsel, 8]
+ *   with psam_mask_stats' fields and empty-mask values, box in the OH x OW image's frame.
+ * psam_mask_binarize_resized: mask i = plane idx[i] of low viewed as [planes,IN,IN], written as {0,1} into the rectangle
+ *   [y0, y0+OH) x [x0, x0+OW) of frame i of out uint8 [n,FH,FW] (uncrop_masks, utils/amg.py:255-265); bytes outside the rectangle
+ *   are not touched. With label uint8 [FH,FW]: counts int64 [n,3] = {tp, fp, fn} over the rectangle (zeroed here).
+ * Planes are the grid's y dimension: B * nsel <= 65535, n <= 65535. PSAM_ERR_ARG for non-positive sizes, ih > MID, iw > MID, a
+ * rectangle outside the frame, first < 0 or first + nsel > C, off < 0, label without counts, more planes than the limit.
+ * automatic_mask_generator.py:293-316; utils/amg.py:156-176, 303-346 */
+int psam_mask_stats_resized(const float* low, int B, int C, int first, int nsel, int IN, int MID, int ih, int iw, int OH, int OW,
+                            int variant, float thr, float off, int* stats, void* stream);
+/* psam_mask_stats_resized for the candidates that pass the generator's first filter only: score fp32 [B,C] (the decoder's predicted
+ * IoUs, indexed like low's planes); a plane whose score fails `score > (float)score_thresh` (NaN fails) keeps the empty-mask row and
+ * costs nothing. The generator drops those candidates before it reads their statistics (automatic_mask_generator.py:293-295), on
+ * the host and in psam_amg_select with this same float32 comparison. score = NULL is refused. */
+int psam_mask_stats_resized_scored(const float* low, const float* score, double score_thresh, int B, int C, int first, int nsel,
+                                   int IN, int MID, int ih, int iw, int OH, int OW, int variant, float thr, float off, int* stats,
+                                   void* stream);
+int psam_mask_binarize_resized(const float* low, const int* idx, int n, int IN, int MID, int ih, int iw, int OH, int OW, int variant,
+                               float thr, unsigned char* out, int FH, int FW, int y0, int x0, const unsigned char* label,
+                               long long* counts, void* stream);
 
 /* Uncompressed COCO run-length code of binary masks uint8 [n,H,W] (any non-zero byte is set), on the device: pixels in
  * column-major order p = x*H + y, counts alternate zero-run / one-run lengths and start with a zero-run (a set first pixel

@@ -109,6 +109,10 @@ SIGNATURES = {
                         c_void_p, c_void_p],
     "psam_mask_binarize": [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p,
                            c_void_p, c_void_p],
+    "psam_mask_stats_resized": [c_void_p] + [c_int] * 11 + [c_float, c_float, c_void_p, c_void_p],
+    "psam_mask_stats_resized_scored": [c_void_p, c_void_p, ctypes.c_double] + [c_int] * 11 + [c_float, c_float, c_void_p, c_void_p],
+    "psam_mask_binarize_resized": [c_void_p, c_void_p] + [c_int] * 8 + [c_float, c_void_p, c_int, c_int, c_int, c_int, c_void_p,
+                                   c_void_p, c_void_p],
     "psam_normalize_chw": [c_void_p, c_int, c_int, c_longlong, ctypes.POINTER(c_float), ctypes.POINTER(c_float),
                            c_void_p, c_void_p],
     "psam_ccl": [c_void_p, c_void_p, c_int, c_int, c_int] + [c_void_p] * 9 + [c_void_p],

@@ -1220,6 +1220,58 @@ def mask_binarize(low, idx, MID, H, W, variant, thr=0.0, label=None, out=None):
     return out, counts
 
 
+def mask_stats_resized(low, first, nsel, MID, in_size, out_size, variant, thr=0.0, off=1.0, stats=None, score=None,
+                       score_thresh=0.0):
+    """mask_stats for an image that is not at the model's input size: int32 [B*nsel, 8] over the out_size = (OH, OW) image, whose
+    pixels are the second resize of postprocess_masks - from the in_size = (ih, iw) corner of the MID x MID up-sampling - computed
+    on the fly from low [B,C,IN,IN]. The bits of mask_upsample -> crop -> resize2d -> plane_stats. With `score` fp32 [B,C] (the
+    decoder's predicted IoUs) and score_thresh > 0, planes whose score is not above float32(score_thresh) are skipped and keep the
+    empty-mask row: the generator's first filter drops them whatever their statistics."""
+    _req(low, torch.float32, "low")
+    assert low.is_contiguous() and low.dim() == 4
+    B, C, IN, _ = low.shape
+    (ih, iw), (OH, OW) = (int(v) for v in in_size), (int(v) for v in out_size)
+    if stats is None:
+        stats = torch.empty((B * nsel, 8), dtype=torch.int32, device=low.device)
+    assert stats.dtype == torch.int32 and stats.is_contiguous() and stats.numel() >= B * nsel * 8
+    if score is not None and score_thresh > 0.0:
+        _req(score, torch.float32, "score")
+        assert score.is_contiguous() and tuple(score.shape) == (B, C)
+        st = _lib.lib().psam_mask_stats_resized_scored(_ptr(low), _ptr(score), float(score_thresh), B, C, first, nsel, IN, MID, ih, iw,
+                                                       OH, OW, variant, float(thr), float(off), _ptr(stats), _stream())
+        _lib.check(st, "psam_mask_stats_resized_scored")
+        return stats
+    st = _lib.lib().psam_mask_stats_resized(_ptr(low), B, C, first, nsel, IN, MID, ih, iw, OH, OW, variant, float(thr), float(off),
+                                            _ptr(stats), _stream())
+    _lib.check(st, "psam_mask_stats_resized")
+    return stats
+
+
+def mask_binarize_resized(low, idx, MID, in_size, out_size, variant, thr=0.0, label=None, out=None, origin=(0, 0)):
+    """mask_binarize with the second resize of postprocess_masks: mask i = (plane idx[i] of low.view(-1,IN,IN), up-sampled to MID,
+    cropped to in_size = (ih, iw), resized to out_size = (OH, OW)) > thr, written into the rectangle of that size at origin = (y0, x0)
+    of frame i of `out` uint8 [n,FH,FW]. A new `out` is [n,y0+OH,x0+OW] and zero outside the rectangle; a given one keeps its bytes
+    there. With `label` uint8 [FH,FW] also int64 [n,3] {tp,fp,fn} over the rectangle."""
+    _req(low, torch.float32, "low"); _req(idx, torch.int32, "idx")
+    assert low.is_contiguous() and idx.is_contiguous()
+    IN, n = low.shape[-1], idx.numel()
+    (ih, iw), (OH, OW), (y0, x0) = (int(v) for v in in_size), (int(v) for v in out_size), (int(v) for v in origin)
+    if out is None:
+        make = torch.empty if (y0, x0) == (0, 0) else torch.zeros
+        out = make((n, y0 + OH, x0 + OW), dtype=torch.uint8, device=low.device)
+    assert out.dtype == torch.uint8 and out.is_contiguous() and out.dim() == 3 and out.shape[0] >= n
+    FH, FW = out.shape[1:]
+    counts = None
+    if label is not None:
+        _req(label, torch.uint8, "label")
+        assert label.is_contiguous() and tuple(label.shape) == (FH, FW)
+        counts = torch.empty((n, 3), dtype=torch.int64, device=low.device)
+    st = _lib.lib().psam_mask_binarize_resized(_ptr(low), _ptr(idx), n, IN, MID, ih, iw, OH, OW, variant, float(thr), _ptr(out), FH,
+                                               FW, y0, x0, _ptr(label), _ptr(counts), _stream())
+    _lib.check(st, "psam_mask_binarize_resized")
+    return out, counts
+
+
 NMS_MAX_GROUP = 16384   # candidates psam_box_nms / psam_amg_select take per group (csrc/nms.hip)
 AMG_REC = 9             # int32 words of a psam_amg_select record: candidate, plane, IoU bits, stability bits, area, x0, y0, x1, y1
 _nms_scratch = {}

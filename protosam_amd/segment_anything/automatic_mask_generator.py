@@ -17,12 +17,27 @@ run lengths cross to the host - no full-size mask is downloaded.
 with the default, the second half of every `points_per_batch` batch is labelled as NEGATIVE points. `custom_points=False`
 gives upstream SAM's behaviour.
 
-Crop layers (`crop_n_layers > 0`, :194-262), images whose long side is not the model's input size, and
-`min_mask_region_area > 0` (:332-380) take the general path (`_generate_general`): every crop is re-encoded; its candidates
-take the SECOND resize of `postprocess_masks`, so the ones that pass the predicted-IoU filter are materialised at the crop's
-resolution in chunks and reduced by `psam_plane_stats` (counts, box, binary mask in one pass); edge filter, per-crop and
-cross-crop NMS on the host over the statistics; holes / islands below the area threshold are found with the device
-connected-components kernel (`psam_ccl`; the reference loops over masks with cv2, utils/amg.py:267-291).
+An image whose long side is not the model's input size takes the same fused path, through every entry point (`generate`,
+`generate_device`, `generate_batch`, `generate_device_batch`): its masks take the SECOND resize of `postprocess_masks`
+(sam.py:132-160), which `psam_mask_stats_resized` / `psam_mask_binarize_resized` (csrc/amg_resize.hip) compute per output
+pixel together with the first one - the bits of `psam_mask_upsample` -> crop -> `psam_resize2d`, nothing written in between.
+The statistics kernel is given the predicted IoUs and skips the candidates that the first filter drops whatever their statistics
+(`psam_mask_stats_resized_scored`): their rows hold the empty-mask values and are never read.
+Images at the model's size run `psam_mask_stats` / `psam_mask_binarize` as before (`_fast_path`).
+
+Crop layers (`crop_n_layers > 0`, :194-262) and `min_mask_region_area > 0` (:332-380) take the general path
+(`_generate_general`): every crop is re-encoded; one statistics table for all 3n candidates of the crop comes straight from
+its logits (`_crop_fused`), one download, then predicted-IoU, stability and edge filter and the per-crop NMS on the host in
+the reference's order, and only the NMS survivors are binarised - into zeroed frames of the original image at the crop's
+offset (uncrop_masks); cross-crop NMS on the host; holes / islands below the area threshold are found with the device
+connected-components kernel (`psam_ccl`; the reference loops over masks with cv2, utils/amg.py:267-291). What stays as it was:
+a crop's candidates are selected on the host (the edge filter is not in `psam_amg_select`), and the small-region stage works
+on materialised masks.
+
+`PSAM_AMG_RESIZE=materialise` (read in the constructor, default `fused`) selects the earlier route for any-size images and
+crops: the candidates that pass the predicted-IoU filter are written at full size in chunks of 64 (`postprocess_masks`) and
+reduced by `psam_plane_stats` (counts, box, binary mask in one pass). Both routes return the same records; the tests and
+tools/bench_amg_anysize.py compare them.
 output_mode "coco_rle" keeps the reference's contract: the constructor imports pycocotools and raises the same ImportError
 without it (:116-117); with it, the segmentation is `coco_encode_rle` of the uncompressed RLE (:181-183), which is this
 project's own restatement of the COCO string form. Without the package, `coco_encode_rle(rec["segmentation"])` on the
@@ -74,6 +89,12 @@ class SamAutomaticMaskGenerator:
         self.amg_select = os.environ.get("PSAM_AMG_SELECT", "host")
         if self.amg_select not in ("host", "device"):
             raise ValueError(f"PSAM_AMG_SELECT must be 'host' or 'device', got {self.amg_select!r}")
+        # how images that are not at the model's input size, and crops, get their statistics and masks: "fused" (the default:
+        # psam_mask_stats_resized / psam_mask_binarize_resized, both resizes of postprocess_masks per pixel, nothing written in
+        # between) or "materialise" (postprocess_masks writes every filtered candidate at full size, psam_plane_stats reduces it)
+        self.amg_resize = os.environ.get("PSAM_AMG_RESIZE", "fused")
+        if self.amg_resize not in ("fused", "materialise"):
+            raise ValueError(f"PSAM_AMG_RESIZE must be 'fused' or 'materialise', got {self.amg_resize!r}")
         self._low = None
 
     def to(self, device):  # models/SamWrapper.py:52-54 calls this
@@ -112,7 +133,8 @@ class SamAutomaticMaskGenerator:
         sam = pr.model
         h, w = image.shape[:2]
         pr.set_image(image)                                                     # :239
-        assert tuple(pr.input_size) == (h, w)                                   # (other sizes take _generate_general)
+        in_size = tuple(int(v) for v in pr.input_size)
+        assert in_size == self._input_size(h, w)
         pts = self.point_grids[0] * np.array([[w, h]], dtype=np.float64)        # :241-243
         n = len(pts)
         labels = self._point_labels(n)
@@ -135,7 +157,11 @@ class SamAutomaticMaskGenerator:
                                                   masks_out=low[lo:hi], iou_out=iou[lo:hi])
         pr.reset_image()                                                        # :260
         thr = float(sam.mask_threshold)
-        stats = ops.mask_stats(low, 1, 3, S, h, w, sam.variant_id(), thr, self.stability_score_offset)
+        if in_size == (h, w):
+            stats = ops.mask_stats(low, 1, 3, S, h, w, sam.variant_id(), thr, self.stability_score_offset)
+        else:   # the second resize of postprocess_masks, on the fly; candidates the predicted-IoU filter drops anyway are skipped
+            stats = ops.mask_stats_resized(low, 1, 3, S, in_size, (h, w), sam.variant_id(), thr, self.stability_score_offset,
+                                           score=iou, score_thresh=self.pred_iou_thresh)
         return dict(pts=pts, size=(h, w), n=n, low=low, iou=iou, stats=stats)
 
     def _select_host(self, ctx):
@@ -200,15 +226,32 @@ class SamAutomaticMaskGenerator:
         h, w = cand["size"]
         if cand["plane"].numel() == 0:
             return torch.empty((0, h, w), dtype=torch.uint8, device=low.device), None
-        return ops.mask_binarize(low, cand["plane"], sam.image_encoder.img_size, h, w, sam.variant_id(),
-                                 float(sam.mask_threshold), label=label)
+        S = sam.image_encoder.img_size
+        in_size = self._input_size(h, w)
+        if in_size == (h, w):
+            return ops.mask_binarize(low, cand["plane"], S, h, w, sam.variant_id(), float(sam.mask_threshold), label=label)
+        return ops.mask_binarize_resized(low, cand["plane"], S, in_size, (h, w), sam.variant_id(), float(sam.mask_threshold),
+                                         label=label)
 
-    # ---- general path: crop layers, any image size, small-region removal -----------------------------------------------------
+    def _input_size(self, h, w):
+        """`predictor.input_size` of an h x w image: its size once the long side is the model's (ResizeLongestSide)."""
+        S = self.predictor.model.image_encoder.img_size
+        return tuple(int(v) for v in self.predictor.transform.get_preprocess_shape(h, w, S))
+
+    # ---- general path: crop layers, small-region removal, PSAM_AMG_RESIZE=materialise -----------------------------------------
     def _fast_path(self, image):
-        """Layer-0 crop only, image already at the model's input size (what SamWrapper.forward produces): the fused path."""
+        """Layer-0 crop only, image already at the model's input size (what SamWrapper.forward produces): the fused path without a
+        second resize, which is what `SamWrapper.forward_batch` chains its own kernels behind."""
         h, w = image.shape[:2]
         S = self.predictor.model.image_encoder.img_size
         return self.crop_n_layers == 0 and self.min_mask_region_area == 0 and max(h, w) == S
+
+    def _fused_path(self, image):
+        """Layer-0 crop only, no small-region stage: the fused path, at any image size unless PSAM_AMG_RESIZE=materialise keeps
+        images that need the second resize on the general path."""
+        if self.amg_resize == "fused":
+            return self.crop_n_layers == 0 and self.min_mask_region_area == 0
+        return self._fast_path(image)
 
     def _decode_points(self, pts, im_size):
         """All grid points of the image set on the predictor -> self._low [n,4,256,256], self._iou [n,4] (device)."""
@@ -250,6 +293,8 @@ class SamAutomaticMaskGenerator:
         self._decode_points(pts, (ch, cw))
         in_size = tuple(pr.input_size)
         pr.reset_image()
+        if self.amg_resize == "fused":
+            return self._crop_fused(pts, crop_box, tuple(int(v) for v in in_size), orig_size)
         dev = self._low.device
         thr = float(sam.mask_threshold)
         n = len(pts)
@@ -285,6 +330,49 @@ class SamAutomaticMaskGenerator:
         full_masks = torch.zeros((len(order), H, W), dtype=torch.uint8, device=dev)   # uncrop_masks
         if len(order):
             full_masks[:, y0:y1, x0:x1] = masks[torch.from_numpy(order).to(dev)]
+        return dict(iou_preds=iou[kept][order], stability_score=stab[order], boxes=boxes[order] + np.array([[x0, y0, x0, y0]]),
+                    area=area[order], points=pts[kept[order] // 3] + np.array([[x0, y0]], dtype=np.float64),
+                    crop_boxes=np.tile(np.array([crop_box], dtype=np.int64), (len(order), 1)), masks=full_masks)
+
+    def _crop_fused(self, pts, crop_box, in_size, orig_size):
+        """`_process_crop` after the decoder, without a full-resolution candidate: one statistics table for all 3n candidates
+        straight from the logits, one download, the host filters and NMS in `_process_crop`'s order, and only the NMS survivors
+        binarised - into zeroed frames of the ORIGINAL image at the crop's offset (uncrop_masks). The same dict."""
+        sam = self.predictor.model
+        H, W = orig_size
+        x0, y0, x1, y1 = crop_box
+        ch, cw = y1 - y0, x1 - x0
+        dev = self._low.device
+        S, variant, thr = sam.image_encoder.img_size, sam.variant_id(), float(sam.mask_threshold)
+        n = len(pts)
+        if in_size == (ch, cw):
+            stats = ops.mask_stats(self._low, 1, 3, S, ch, cw, variant, thr, self.stability_score_offset)
+        else:
+            stats = ops.mask_stats_resized(self._low, 1, 3, S, in_size, (ch, cw), variant, thr, self.stability_score_offset,
+                                           score=self._iou, score_thresh=self.pred_iou_thresh)
+        host = torch.cat([stats.view(-1), self._iou.view(torch.int32).view(-1)]).cpu().numpy()   # the one download
+        st = host[:3 * n * 8].reshape(3 * n, 8)
+        iou = np.ascontiguousarray(host[3 * n * 8:].view(np.float32).reshape(n, 4)[:, 1:]).reshape(-1)
+        cand = np.arange(3 * n)
+        if self.pred_iou_thresh > 0.0:
+            cand = cand[iou[cand] > self.pred_iou_thresh]
+        st = st[cand]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            stab = st[:, 0].astype(np.float32) / st[:, 1].astype(np.float32)
+        ok = np.ones(len(st), bool)
+        if self.stability_score_thresh > 0.0:
+            ok &= stab >= self.stability_score_thresh
+        boxes = st[:, 3:7].astype(np.int64)
+        boxes[st[:, 2] == 0] = 0
+        ok &= ~is_box_near_crop_edge(boxes, crop_box, [0, 0, W, H])             # :309-311
+        idx = np.flatnonzero(ok)
+        kept, stab, boxes, area = cand[idx], stab[idx], boxes[idx], st[idx, 2]
+        order = nms_xyxy(boxes, iou[kept], self.box_nms_thresh)                 # :244-250
+        full_masks = torch.zeros((len(order), H, W), dtype=torch.uint8, device=dev)   # uncrop_masks
+        if len(order):
+            planes = (kept[order] // 3) * 4 + 1 + kept[order] % 3
+            ops.mask_binarize_resized(self._low, torch.from_numpy(planes.astype(np.int32)).to(dev), S, in_size, (ch, cw), variant,
+                                      thr, out=full_masks, origin=(y0, x0))
         return dict(iou_preds=iou[kept][order], stability_score=stab[order], boxes=boxes[order] + np.array([[x0, y0, x0, y0]]),
                     area=area[order], points=pts[kept[order] // 3] + np.array([[x0, y0]], dtype=np.float64),
                     crop_boxes=np.tile(np.array([crop_box], dtype=np.int64), (len(order), 1)), masks=full_masks)
@@ -397,7 +485,7 @@ class SamAutomaticMaskGenerator:
         uncompressed RLE {"size", "counts": [ints]} ("uncompressed_rle") or its COCO string form ("coco_rle", needs
         pycocotools at construction as in the reference; `utils.amg.coco_encode_rle(rec["segmentation"])` on the
         "uncompressed_rle" records gives the same COCO record without the package)."""
-        if not self._fast_path(image):
+        if not self._fused_path(image):
             data, masks = self._generate_general(image)
             masks = self._segmentations(masks)
             anns = []
@@ -452,7 +540,7 @@ class SamAutomaticMaskGenerator:
 
         k = 0
         for i, image in enumerate(images):
-            if not self._fast_path(image):
+            if not self._fused_path(image):
                 drain()
                 out[i] = fallback(i)
                 continue
@@ -508,7 +596,7 @@ class SamAutomaticMaskGenerator:
     def generate_device(self, image, label=None):
         """Device-resident variant for callers that reduce the masks further: -> (candidate dict, uint8 masks [n,H,W] on
         the device, int64 [n,3] {tp, fp, fn} against `label` or None)."""
-        if not self._fast_path(image):
+        if not self._fused_path(image):
             data, masks = self._generate_general(image)
             counts = None
             if label is not None:   # {tp, fp, fn} of every record against the label (models/SamWrapper.py:8-13), on the device
