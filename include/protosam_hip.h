@@ -486,6 +486,36 @@ int psam_box_nms(const void* boxes, int boxes_fp32, const float* scores, const i
 int psam_amg_select(const int* stats, const float* iou4, const int* offsets, int n, int G, int max_group, double pred_iou_thresh,
                     double stability_thresh, double nms_thresh, int* records, int cap, int* count, void* scratch,
                     long long scratch_bytes, void* stream);
+/* psam_amg_select for the candidates of one crop (automatic_mask_generator.py:309-311): a candidate that passes the score filters
+ * is also dropped when its box is near a crop edge, utils/amg.py:199-206 in integers - with v = box[k] + crop_box[k % 2] (the box in
+ * the image's frame), some k has |v - crop_box[k]| <= 20 and not |v - orig_box[k]| <= 20. The box is stats[3..6], or [0,0,0,0]
+ * where stats[2] == 0, as everywhere else; the records keep boxes in the crop's frame. crop_box, orig_box: HOST int[4], XYXY (the
+ * crop inside the image, and [0, 0, W, H]); NULL is status 1. Everything else as psam_amg_select. */
+int psam_amg_select_crop(const int* stats, const float* iou4, const int* offsets, int n, int G, int max_group,
+                         double pred_iou_thresh, double stability_thresh, double nms_thresh, const int* crop_box,
+                         const int* orig_box, int* records, int cap, int* count, void* scratch, long long scratch_bytes,
+                         void* stream);
+
+/* ---- small-region removal for a batch of masks (csrc/small_regions.hip) --------------------------------------------------
+ * Per mask, bit for bit remove_small_regions(mask, t, "holes") then remove_small_regions(., t, "islands")
+ * (segment_anything/utils/amg.py:267-291; the stage of automatic_mask_generator.py:332-380), 8-connected:
+ *   holes   : every region of the complement with (double)area < area_thresh is filled, the outer background included;
+ *             changed_holes = such a region exists.
+ *   islands : on the filled mask; if no foreground region is below the threshold nothing changes, otherwise every such region is
+ *             dropped, and if that drops all of them the largest stays (among equal largest: the one whose first pixel comes first
+ *             in raster order). changed_islands = a region below the threshold exists.
+ * masks uint8 [m,H,W], 0 / non-0 -> out uint8 [m,H,W], 0 / 1 (equal to the input's 0 / 1 form where nothing changed);
+ * info int32 [m,4] = {changed_holes, changed_islands, area of out, 0}; boxes int32 [m,4] = XYXY min / max of out, {0,0,0,0} for
+ * an empty mask; scores fp32 [m] = 1 if neither flag is set, else 0 (the reference's float(not changed)) - boxes and scores as
+ * psam_box_nms reads them. Regions are counted per union-find root: there is no limit on their number.
+ * The m masks are walked in chunks of `chunk` (<= 65535 per launch), every launch enqueued, no host wait: scratch holds a chunk,
+ * psam_small_regions_workspace bytes = chunk * (8 * H * W + 64), 8-byte aligned. Eleven stream-ordered launches per chunk; no
+ * flags or waits between workgroups.
+ * Status 1 before any launch: m < 0, H or W <= 0, H * W beyond int32 (or H * (W rounded up to 256) beyond 2^32 - 1), chunk < 1,
+ * a NaN threshold, and with m > 0 a NULL pointer, misaligned or short scratch. m == 0 does nothing and returns 0. */
+int psam_small_regions_workspace(int H, int W, int chunk, long long* bytes);
+int psam_small_regions(const void* masks, int m, int H, int W, double area_thresh, int chunk, void* out, int* boxes, float* scores,
+                       int* info, void* scratch, long long scratch_bytes, void* stream);
 
 /* Slice hand-off from a scan volume (raw NIfTI voxels [Z,H,W]; vol_dtype 0 int16, 1 float32, 2 uint8, 3 int32).
  * psam_volume_stats: out[0] = sum(x), out[1] = sum(x^2) in fp64, x = voxel*slope + inter  (MR_normalize / get_CT_statistics,

@@ -97,6 +97,11 @@ SIGNATURES = {
                      c_longlong, c_void_p],
     "psam_amg_select": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                         c_void_p, c_int, c_void_p, c_void_p, c_longlong, c_void_p],
+    "psam_amg_select_crop": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                             ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_void_p, c_int, c_void_p, c_void_p, c_longlong, c_void_p],
+    "psam_small_regions_workspace": [c_int, c_int, c_int, ctypes.POINTER(c_longlong)],
+    "psam_small_regions": [c_void_p, c_int, c_int, c_int, ctypes.c_double, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                           c_longlong, c_void_p],
     "psam_mask_counts": [c_void_p, c_int, c_void_p, c_int, c_void_p] + [c_int] * 6 + [c_float, c_void_p, c_void_p, c_void_p],
     "psam_best_iou": [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p],
     "psam_mask_downscale": [c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p],

@@ -16,35 +16,10 @@
 // tab[3] = index (0-based) of the most confident component, then per component k at tab[8 + 12*k ..]:
 //   {area, sum_x, sum_y, min_x, min_y, max_x, max_y, conf, best_x, best_y, best_p, 0}
 #include "common.h"
+#include "ccl_uf.h"   // uf_find / uf_union, the run-start init and the reduced merges (shared with small_regions.hip)
 
 #define CC_STRIDE 12
 #define CC_HDR 8
-
-__device__ __forceinline__ int uf_find(const int* parent, int a) {
-  int p = parent[a];
-  while (p != a) {
-    a = p;
-    p = parent[a];
-  }
-  return a;
-}
-
-__device__ __forceinline__ void uf_union(int* parent, int a, int b) {
-  for (;;) {
-    a = uf_find(parent, a);
-    b = uf_find(parent, b);
-    if (a == b) return;
-    if (a < b) {
-      int t = a;
-      a = b;
-      b = t;
-    }
-    // a > b: hang a under b if a is still a root
-    int old = atomicMin(&parent[a], b);
-    if (old == a) return;
-    a = old;  // somebody re-parented a concurrently; retry from its new parent
-  }
-}
 
 // Batched form (psam_ccl_batch): blockIdx.z = image of the batch, every array moves by its per-image stride (elements); the
 // single-image entry launches with grid.z = 1 and zero strides.
@@ -60,24 +35,13 @@ __global__ __launch_bounds__(256) void ccl_init_kernel(const uint8_t* __restrict
     counters[0] = 0;
     counters[1] = 0;
   }
-  const int lane = threadIdx.x & 63;
   const bool fg = x < W && pred[(size_t)y * W + x] != 0;
-  const unsigned long long mask = __ballot(fg);
+  const int par = uf_run_start(fg, x, y, W, threadIdx.x & 63);
   if (x >= W) return;
-  int par = -1;
-  if (fg) {
-    const unsigned long long below = lane ? (~mask & ((1ull << lane) - 1ull)) : 0ull;  // background lanes left of me
-    const int start = below ? 64 - __clzll((long long)below) : 0;
-    par = y * W + (x - lane) + start;
-  }
   parent[(size_t)y * W + x] = par;
 }
 
-// merge: unions only where connectivity is not already implied by a horizontal run (Playne/Hawick-style reduction):
-//   W  : only for the first lane of a segment (runs crossing a 64-pixel boundary)
-//   N  : unless W and NW are both foreground (then W already linked to NW, which is in N's run)
-//   NW : only if N and W are background
-//   NE : only if N is background
+// merge: the reduced set of unions of uf_merge_pixel (ccl_uf.h)
 __global__ __launch_bounds__(256) void ccl_merge_kernel(const uint8_t* __restrict__ pred, int H, int W,
                                                         int* __restrict__ parent, CclStride st) {
   pred += blockIdx.z * st.pred; parent += blockIdx.z * st.parent;
@@ -85,19 +49,7 @@ __global__ __launch_bounds__(256) void ccl_merge_kernel(const uint8_t* __restric
   if (x >= W) return;
   const int p = y * W + x;
   if (!pred[p]) return;
-  const bool w = x > 0 && pred[p - 1];
-  if (w && (threadIdx.x & 63) == 0) uf_union(parent, p, p - 1);
-  if (y == 0) return;
-  const int q = p - W;
-  const bool n = pred[q] != 0;
-  const bool nw = x > 0 && pred[q - 1];
-  const bool ne = x + 1 < W && pred[q + 1];
-  if (n) {
-    if (!(w && nw)) uf_union(parent, p, q);
-  } else {
-    if (nw && !w) uf_union(parent, p, q - 1);
-    if (ne) uf_union(parent, p, q + 1);
-  }
+  uf_merge_pixel(parent, p, x, y, W, (threadIdx.x & 63) == 0, [&](int q) { return pred[q] != 0; });
 }
 
 // flatten: parent[i] := the root of i, and the roots are collected. One pass (round 5; rounds 1-4 ran a read-only find here and a second

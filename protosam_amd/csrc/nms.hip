@@ -7,7 +7,8 @@
 //
 // Candidates come in G groups (group g = rows offsets[g] .. offsets[g+1] of the inputs), at most NMS_MAX_GROUP per group.
 // Per call, ordered by separate launches on one stream (no flags, no waits between workgroups, every loop bounded by the group):
-//   1. nms_prep_kernel / amg_prep_kernel: one thread per candidate -> its fp32 box and its 64-bit key; 0 = filtered out.
+//   1. nms_prep_kernel / amg_prep_kernel: one thread per candidate -> its fp32 box and its 64-bit key; 0 = filtered out
+//      (psam_amg_select_crop: also where the box is near a crop edge, is_box_near_crop_edge).
 //      key = order-preserving transform of the score's bits << 32 | ~index: all keys of a group differ, larger score first,
 //      lower index first among equal scores (argsort(-s, kind="stable"); -0.0 is keyed as +0.0), whatever the scheduling.
 //   2. nms_rank_kernel: rank = number of larger keys of the group (tiles of 256 keys through LDS; <= 2^28 comparisons at the
@@ -107,11 +108,27 @@ __global__ __launch_bounds__(256) void nms_prep_kernel(const void* __restrict__ 
   s.key[o] = nms_key(scores[c], i);
 }
 
+// psam_amg_select_crop: the crop's box and the image's box (XYXY, pixels) of is_box_near_crop_edge; use = 0 for psam_amg_select
+struct AmgCrop { int use; int crop[4]; int orig[4]; };
+
+// utils/amg.py:199-206 for integer pixel coordinates: the box, moved by the crop's origin into the image's frame, has an edge
+// within 20 pixels of the crop's edge that is not within 20 pixels of the image's edge
+__device__ __forceinline__ bool amg_near_crop_edge(const int b[4], const AmgCrop& c) {
+  bool near = false;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const long long v = (long long)b[k] + c.crop[k & 1];
+    const long long dc = v - c.crop[k], di = v - c.orig[k];
+    near = near || ((dc < 0 ? -dc : dc) <= 20 && !((di < 0 ? -di : di) <= 20));
+  }
+  return near;
+}
+
 // The two score filters and the box rule of automatic_mask_generator.py:125-133 in front of the same keys. stats int32 [M, 8] as
 // psam_mask_stats writes it; iou4 fp32 [M / 3 rounded up, 4]: candidate c's predicted IoU is row c / 3, column 1 + c % 3.
 __global__ __launch_bounds__(256) void amg_prep_kernel(const int* __restrict__ stats, const float* __restrict__ iou4,
                                                        const int* __restrict__ offsets, int n, int maxg, int use_iou, float iou_thr,
-                                                       int use_stab, float stab_thr, NmsScratch s) {
+                                                       int use_stab, float stab_thr, AmgCrop crop, NmsScratch s) {
   const int g = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
   int base;
   const int m = nms_group(offsets, g, n, maxg, &base);
@@ -123,8 +140,10 @@ __global__ __launch_bounds__(256) void amg_prep_kernel(const int* __restrict__ s
   bool ok = true;
   if (use_iou) ok = iou > iou_thr;                // float32 > float32, as numpy compares a float32 array with a Python float
   if (use_stab) ok = ok && stab >= stab_thr;      // NaN (0 / 0) fails
-  float4 b = make_float4(0.f, 0.f, 0.f, 0.f);     // empty mask -> [0, 0, 0, 0]
-  if (st[2] != 0) b = make_float4((float)st[3], (float)st[4], (float)st[5], (float)st[6]);
+  int bi[4] = {0, 0, 0, 0};                       // empty mask -> [0, 0, 0, 0]
+  if (st[2] != 0) { bi[0] = st[3]; bi[1] = st[4]; bi[2] = st[5]; bi[3] = st[6]; }
+  if (crop.use) ok = ok && !amg_near_crop_edge(bi, crop);   // :309-311, after the score filters as on the host
+  const float4 b = make_float4((float)bi[0], (float)bi[1], (float)bi[2], (float)bi[3]);
   s.ubox[o] = b;
   s.key[o] = ok ? nms_key(iou, i) : 0ull;
 }
@@ -270,9 +289,9 @@ extern "C" int psam_box_nms(const void* boxes, int boxes_fp32, const float* scor
   return psam_launch_status();
 }
 
-extern "C" int psam_amg_select(const int* stats, const float* iou4, const int* offsets, int n, int G, int max_group,
-                               double pred_iou_thresh, double stability_thresh, double nms_thresh, int* records, int cap,
-                               int* count, void* scratch, long long scratch_bytes, void* stream) {
+static int amg_select_launch(const int* stats, const float* iou4, const int* offsets, int n, int G, int max_group,
+                             double pred_iou_thresh, double stability_thresh, double nms_thresh, const AmgCrop& crop, int* records,
+                             int cap, int* count, void* scratch, long long scratch_bytes, void* stream) {
   if (!nms_args_ok(n, G, max_group, cap, scratch, scratch_bytes) || !offsets || !records || !count || (n > 0 && (!stats || !iou4)) ||
       nms_thresh != nms_thresh || pred_iou_thresh != pred_iou_thresh || stability_thresh != stability_thresh)
     return PSAM_ERR_ARG;
@@ -282,11 +301,36 @@ extern "C" int psam_amg_select(const int* stats, const float* iou4, const int* o
   const dim3 per((unsigned)((maxg + 255) / 256), (unsigned)G);
   const int reach = cap < maxg ? cap : maxg;
   hipLaunchKernelGGL(amg_prep_kernel, per, dim3(256), 0, st, stats, iou4, offsets, n, maxg, pred_iou_thresh > 0.0 ? 1 : 0,
-                     (float)pred_iou_thresh, stability_thresh > 0.0 ? 1 : 0, (float)stability_thresh, s);
+                     (float)pred_iou_thresh, stability_thresh > 0.0 ? 1 : 0, (float)stability_thresh, crop, s);
   hipLaunchKernelGGL(nms_rank_kernel, per, dim3(256), 0, st, offsets, n, maxg, s);
   hipLaunchKernelGGL(nms_walk_kernel, dim3((unsigned)G), dim3(NMS_WALK_THREADS), 0, st, s, maxg, nms_thresh, s.kept, (long long)maxg,
                      maxg, count);
   hipLaunchKernelGGL(amg_records_kernel, dim3((unsigned)((reach + 255) / 256), (unsigned)G), dim3(256), 0, st, stats, iou4, offsets, s,
                      maxg, cap, count, records);
   return psam_launch_status();
+}
+
+extern "C" int psam_amg_select(const int* stats, const float* iou4, const int* offsets, int n, int G, int max_group,
+                               double pred_iou_thresh, double stability_thresh, double nms_thresh, int* records, int cap,
+                               int* count, void* scratch, long long scratch_bytes, void* stream) {
+  AmgCrop crop = {};
+  return amg_select_launch(stats, iou4, offsets, n, G, max_group, pred_iou_thresh, stability_thresh, nms_thresh, crop, records, cap,
+                           count, scratch, scratch_bytes, stream);
+}
+
+// psam_amg_select for the candidates of a crop: one more condition in the prep kernel, a candidate whose box is near a crop edge
+// (amg_near_crop_edge) gets key 0. crop_box / orig_box: HOST int[4], XYXY; the boxes of the records stay in the crop's frame.
+extern "C" int psam_amg_select_crop(const int* stats, const float* iou4, const int* offsets, int n, int G, int max_group,
+                                    double pred_iou_thresh, double stability_thresh, double nms_thresh, const int* crop_box,
+                                    const int* orig_box, int* records, int cap, int* count, void* scratch, long long scratch_bytes,
+                                    void* stream) {
+  if (!crop_box || !orig_box) return PSAM_ERR_ARG;
+  AmgCrop crop;
+  crop.use = 1;
+  for (int k = 0; k < 4; ++k) {
+    crop.crop[k] = crop_box[k];
+    crop.orig[k] = orig_box[k];
+  }
+  return amg_select_launch(stats, iou4, offsets, n, G, max_group, pred_iou_thresh, stability_thresh, nms_thresh, crop, records, cap,
+                           count, scratch, scratch_bytes, stream);
 }

@@ -1348,7 +1348,8 @@ def box_nms(boxes, scores, offsets, iou_threshold, cap=None, kept=None, count=No
     return kept, count
 
 
-def amg_select(stats, iou4, offsets, pred_iou_thresh, stability_score_thresh, box_nms_thresh, cap=None, out=None, scratch=None):
+def amg_select(stats, iou4, offsets, pred_iou_thresh, stability_score_thresh, box_nms_thresh, cap=None, out=None, scratch=None,
+               _crop=None):
     """The generator's score filters and box NMS on the device (psam_amg_select), equal to automatic_mask_generator.py's host lines:
     stats int32 [n,8] (mask_stats), iou4 fp32 [ceil(n/3),4] (the decoder's IoU output, candidate c = row c // 3, column 1 + c % 3),
     `offsets` as box_nms. -> (records int32 [G,cap,AMG_REC], count int32 [G]), both views of ONE int32 tensor `out` of G * cap *
@@ -1373,11 +1374,122 @@ def amg_select(stats, iou4, offsets, pred_iou_thresh, stability_score_thresh, bo
     assert out.is_contiguous() and out.numel() >= words
     records, count = out[:G * cap * AMG_REC].view(G, cap, AMG_REC), out[G * cap * AMG_REC:words]
     scratch = _nms_scratch_for(G, maxg, stats.device, scratch)
-    st = _lib.lib().psam_amg_select(_ptr(stats), _ptr(iou4), _ptr(off_d), n, G, maxg, float(pred_iou_thresh),
-                                    float(stability_score_thresh), float(box_nms_thresh), _ptr(records), cap, _ptr(count),
-                                    _ptr(scratch), scratch.numel() * 8, _stream())
-    _lib.check(st, "psam_amg_select")
+    head = (_ptr(stats), _ptr(iou4), _ptr(off_d), n, G, maxg, float(pred_iou_thresh), float(stability_score_thresh),
+            float(box_nms_thresh))
+    tail = (_ptr(records), cap, _ptr(count), _ptr(scratch), scratch.numel() * 8, _stream())
+    if _crop is None:
+        _lib.check(_lib.lib().psam_amg_select(*head, *tail), "psam_amg_select")
+    else:
+        _lib.check(_lib.lib().psam_amg_select_crop(*head, (_lib.c_int * 4)(*_crop[0]), (_lib.c_int * 4)(*_crop[1]), *tail),
+                   "psam_amg_select_crop")
     return records, count
+
+
+def amg_select_crop(stats, iou4, offsets, pred_iou_thresh, stability_score_thresh, box_nms_thresh, crop_box, orig_box, cap=None,
+                    out=None, scratch=None):
+    """amg_select for the candidates of one crop (psam_amg_select_crop): a candidate whose box is near a crop edge
+    (utils.amg.is_box_near_crop_edge with `crop_box` and `orig_box`, HOST sequences of 4 ints XYXY) is dropped with the score
+    filters. The records keep boxes in the crop's frame. Everything else as amg_select."""
+    cb, ob = tuple(int(v) for v in crop_box), tuple(int(v) for v in orig_box)
+    if len(cb) != 4 or len(ob) != 4:
+        raise ValueError(f"crop_box, orig_box: expected 4 ints each, got {cb} and {ob}")
+    return amg_select(stats, iou4, offsets, pred_iou_thresh, stability_score_thresh, box_nms_thresh, cap=cap, out=out,
+                      scratch=scratch, _crop=(cb, ob))
+
+
+SMALL_REGIONS_BUDGET = 256 << 20    # bytes of scratch small_regions sizes its chunk for (8 bytes per pixel and mask in flight)
+_sr_scratch = {}
+
+
+def small_regions_workspace(H, W, chunk):
+    """Bytes of scratch psam_small_regions needs for `chunk` masks of H x W in flight (psam_small_regions_workspace)."""
+    nbytes = _lib.c_longlong(0)
+    _lib.check(_lib.lib().psam_small_regions_workspace(int(H), int(W), int(chunk), nbytes), "psam_small_regions_workspace")
+    return nbytes.value
+
+
+def small_regions_chunk(m, H, W, budget=None):
+    """Masks in flight for m masks of H x W under a scratch budget in bytes (default SMALL_REGIONS_BUDGET): at least one."""
+    budget = SMALL_REGIONS_BUDGET if budget is None else int(budget)
+    return max(1, min(max(int(m), 1), budget // (8 * H * W + 64)))
+
+
+def small_regions(masks_u8, area_thresh, out=None, chunk=None, scratch=None):
+    """Holes and islands below `area_thresh` pixels removed from m masks at once (psam_small_regions), per mask equal to
+    utils.amg's remove_small_regions(mask, t, "holes") then (., t, "islands"): masks_u8 uint8 [m,H,W] (0 / non-0) ->
+    (out uint8 [m,H,W] 0 / 1, boxes int32 [m,4] XYXY of `out` ([0,0,0,0] for an empty mask), scores fp32 [m] = 1.0 where nothing
+    changed else 0.0, info int32 [m,4] = {changed_holes, changed_islands, area of out, 0}). `chunk`: masks in flight (default: what
+    fits SMALL_REGIONS_BUDGET bytes of scratch, at least one); `scratch`: int64 device tensor of small_regions_workspace bytes
+    (default: cached per shape). Regions are counted per union-find root: no limit on their number."""
+    if masks_u8 is None or not torch.is_tensor(masks_u8):
+        raise TypeError("masks_u8: expected a tensor")
+    _req_rows(masks_u8, torch.uint8, "masks_u8")
+    if masks_u8.dim() != 3 or not masks_u8.is_contiguous():
+        raise ValueError(f"masks_u8: expected a contiguous [m, H, W], got {tuple(masks_u8.shape)}")
+    m, H, W = masks_u8.shape
+    if H <= 0 or W <= 0 or H * W > 0x7fffffff:
+        raise ValueError(f"masks_u8: H and W must be positive with H * W within int32, got {H} x {W}")
+    t = float(area_thresh)
+    if t != t:
+        raise ValueError("area_thresh must not be NaN")
+    if chunk is None:
+        chunk = small_regions_chunk(m, H, W)
+    chunk = int(chunk)
+    if chunk < 1:
+        raise ValueError(f"chunk must be at least 1, got {chunk}")
+    dev = masks_u8.device
+    if out is None:
+        out = torch.empty((m, H, W), dtype=torch.uint8, device=dev)
+    _req_rows(out, torch.uint8, "out")
+    if tuple(out.shape) != (m, H, W) or not out.is_contiguous():
+        raise ValueError(f"out: expected a contiguous {(m, H, W)}, got {tuple(out.shape)}")
+    boxes = torch.empty((m, 4), dtype=torch.int32, device=dev)
+    scores = torch.empty((m,), dtype=torch.float32, device=dev)
+    info = torch.empty((m, 4), dtype=torch.int32, device=dev)
+    need = small_regions_workspace(H, W, chunk)
+    if scratch is None:
+        key = (str(dev), H, W, chunk)
+        if key not in _sr_scratch:
+            _sr_scratch.clear()                      # (one working set at a time: it is sized by a byte budget)
+            _sr_scratch[key] = torch.empty(((need + 7) // 8,), dtype=torch.int64, device=dev)
+        scratch = _sr_scratch[key]
+    if not torch.is_tensor(scratch) or not scratch.is_cuda or scratch.dtype != torch.int64 or not scratch.is_contiguous():
+        raise TypeError("scratch: expected a contiguous int64 device tensor")
+    if scratch.numel() * 8 < need:
+        raise ValueError(f"scratch: {scratch.numel() * 8} bytes, {need} needed for {chunk} masks of {H} x {W} in flight")
+    st = _lib.lib().psam_small_regions(_ptr(masks_u8), m, H, W, t, chunk, _ptr(out), _ptr(boxes), _ptr(scores), _ptr(info),
+                                       _ptr(scratch), scratch.numel() * 8, _stream())
+    _lib.check(st, "psam_small_regions")
+    return out, boxes, scores, info
+
+
+def small_regions_select(masks_u8, area_thresh, nms_thresh, chunk=None, scratch=None):
+    """small_regions and the box NMS of the generator's small-region stage behind it (psam_box_nms, one group, scores 1.0 for
+    unchanged masks and 0.0 for changed ones, so unchanged masks are visited first): -> (out uint8 [m,H,W], table), `table` ONE
+    int32 device tensor of 1 + 9 m words so that a single copy brings the whole decision to the host:
+    table[0] = count kept, table[1:1+m] = kept indices in suppression order (the first `count` are valid),
+    table[1+m:1+5m] = info [m,4], table[1+5m:1+9m] = boxes [m,4]. `small_regions_table(host_table, m)` splits a host copy.
+    More than NMS_MAX_GROUP masks raise."""
+    if masks_u8 is None or not torch.is_tensor(masks_u8):
+        raise TypeError("masks_u8: expected a tensor")
+    m = masks_u8.shape[0] if masks_u8.dim() == 3 else 0
+    if m > NMS_MAX_GROUP:
+        raise ValueError(f"{m} masks exceed the capacity of {NMS_MAX_GROUP} of one NMS group")
+    out, boxes, scores, info = small_regions(masks_u8, area_thresh, chunk=chunk, scratch=scratch)
+    table = torch.empty((1 + 9 * m,), dtype=torch.int32, device=masks_u8.device)
+    if m == 0:
+        table.zero_()
+        return out, table
+    box_nms(boxes, scores, (0, m), nms_thresh, cap=m, kept=table[1:1 + m].view(1, m), count=table[:1])
+    table[1 + m:1 + 5 * m].copy_(info.view(-1))
+    table[1 + 5 * m:].copy_(boxes.view(-1))
+    return out, table
+
+
+def small_regions_table(table, m):
+    """The host copy (numpy int32) of small_regions_select's table -> (kept int64 [count], info [m,4], boxes [m,4])."""
+    count = min(int(table[0]), m)
+    return (table[1:1 + count].astype("int64"), table[1 + m:1 + 5 * m].reshape(m, 4), table[1 + 5 * m:1 + 9 * m].reshape(m, 4))
 
 
 def mask_counts(low, records, count, MID, H, W, variant, label, thr=0.0, counts=None):

@@ -30,9 +30,16 @@ Crop layers (`crop_n_layers > 0`, :194-262) and `min_mask_region_area > 0` (:332
 its logits (`_crop_fused`), one download, then predicted-IoU, stability and edge filter and the per-crop NMS on the host in
 the reference's order, and only the NMS survivors are binarised - into zeroed frames of the original image at the crop's
 offset (uncrop_masks); cross-crop NMS on the host; holes / islands below the area threshold are found with the device
-connected-components kernel (`psam_ccl`; the reference loops over masks with cv2, utils/amg.py:267-291). What stays as it was:
-a crop's candidates are selected on the host (the edge filter is not in `psam_amg_select`), and the small-region stage works
-on materialised masks.
+connected-components kernel (`psam_ccl`; the reference loops over masks with cv2, utils/amg.py:267-291), one mask at a time.
+
+The small-region stage itself runs on the device for all masks at once (`PSAM_AMG_REGIONS=device`, read in the constructor, the
+default): `ops.small_regions_select` (csrc/small_regions.hip: holes and islands of every mask in one kernel chain, areas counted per
+union-find root, so no limit on the number of regions; new areas and boxes from the same passes; `psam_box_nms` behind it) and one
+download of the decision; the masks are then one gather. `PSAM_AMG_REGIONS=host` keeps the per-mask loop described above. Both
+return the same records; profiles/amg_small_regions_bench.txt has the timings behind the default.
+With `PSAM_AMG_SELECT=device` a crop's candidates are selected on the device too (`psam_amg_select_crop`: `psam_amg_select` with
+the crop-edge filter of :309-311): one copy of the records instead of the statistics table, and the binarisation reads its planes
+from the record table. With the default, `host`, a crop is selected on the host as before. Cross-crop NMS stays on the host.
 
 `PSAM_AMG_RESIZE=materialise` (read in the constructor, default `fused`) selects the earlier route for any-size images and
 crops: the candidates that pass the predicted-IoU filter are written at full size in chunks of 64 (`postprocess_masks`) and
@@ -95,6 +102,12 @@ class SamAutomaticMaskGenerator:
         self.amg_resize = os.environ.get("PSAM_AMG_RESIZE", "fused")
         if self.amg_resize not in ("fused", "materialise"):
             raise ValueError(f"PSAM_AMG_RESIZE must be 'fused' or 'materialise', got {self.amg_resize!r}")
+        # the small-region stage (min_mask_region_area > 0): "host" (a Python loop over the masks, two psam_ccl calls and two
+        # downloads per mask, then statistics and nms_xyxy on the host) or "device" (the default: ops.small_regions_select, one
+        # kernel chain for all masks, box NMS on the device, one download). Both give the same records.
+        self.amg_regions = os.environ.get("PSAM_AMG_REGIONS", "device")
+        if self.amg_regions not in ("host", "device"):
+            raise ValueError(f"PSAM_AMG_REGIONS must be 'host' or 'device', got {self.amg_regions!r}")
         self._low = None
 
     def to(self, device):  # models/SamWrapper.py:52-54 calls this
@@ -350,6 +363,8 @@ class SamAutomaticMaskGenerator:
         else:
             stats = ops.mask_stats_resized(self._low, 1, 3, S, in_size, (ch, cw), variant, thr, self.stability_score_offset,
                                            score=self._iou, score_thresh=self.pred_iou_thresh)
+        if self.amg_select == "device":
+            return self._crop_select_device(stats, pts, crop_box, in_size, orig_size)
         host = torch.cat([stats.view(-1), self._iou.view(torch.int32).view(-1)]).cpu().numpy()   # the one download
         st = host[:3 * n * 8].reshape(3 * n, 8)
         iou = np.ascontiguousarray(host[3 * n * 8:].view(np.float32).reshape(n, 4)[:, 1:]).reshape(-1)
@@ -376,6 +391,30 @@ class SamAutomaticMaskGenerator:
         return dict(iou_preds=iou[kept][order], stability_score=stab[order], boxes=boxes[order] + np.array([[x0, y0, x0, y0]]),
                     area=area[order], points=pts[kept[order] // 3] + np.array([[x0, y0]], dtype=np.float64),
                     crop_boxes=np.tile(np.array([crop_box], dtype=np.int64), (len(order), 1)), masks=full_masks)
+
+    def _crop_select_device(self, stats, pts, crop_box, in_size, orig_size):
+        """`_crop_fused` behind the statistics with the selection on the device (PSAM_AMG_SELECT=device): the score filters, the
+        crop-edge filter and the per-crop NMS are `psam_amg_select_crop`, one small copy brings the records and their count to the
+        host, and the binarisation reads its planes from the record table. The same dict."""
+        sam = self.predictor.model
+        H, W = orig_size
+        x0, y0, x1, y1 = crop_box
+        ch, cw = y1 - y0, x1 - x0
+        dev = self._low.device
+        S, variant, thr = sam.image_encoder.img_size, sam.variant_id(), float(sam.mask_threshold)
+        cap = 3 * len(pts)
+        out = torch.empty((cap * ops.AMG_REC + 1,), dtype=torch.int32, device=dev)
+        records, _ = ops.amg_select_crop(stats, self._iou, (0, cap), self.pred_iou_thresh, self.stability_score_thresh,
+                                         self.box_nms_thresh, crop_box, [0, 0, W, H], cap=cap, out=out)
+        cand = self._cand_from_records(dict(n=len(pts), pts=pts, size=(ch, cw)), out.cpu().numpy(), records[0])   # the one copy
+        k = cand["plane"].numel()
+        full_masks = torch.zeros((k, H, W), dtype=torch.uint8, device=dev)      # uncrop_masks
+        if k:
+            ops.mask_binarize_resized(self._low, cand["plane"], S, in_size, (ch, cw), variant, thr, out=full_masks, origin=(y0, x0))
+        return dict(iou_preds=cand["iou_preds"], stability_score=cand["stability_score"],
+                    boxes=cand["boxes"] + np.array([[x0, y0, x0, y0]]), area=cand["area"],
+                    points=cand["points"] + np.array([[x0, y0]], dtype=np.float64),
+                    crop_boxes=np.tile(np.array([crop_box], dtype=np.int64), (k, 1)), masks=full_masks)
 
     def _zero_plane(self, H, W, dev):
         z = getattr(self, "_zero_planes", None)
@@ -429,6 +468,19 @@ class SamAutomaticMaskGenerator:
         new = torch.from_numpy(lut).to(mask_u8.device)[cw.labels.view(H, W).long()]
         return new, True
 
+    def _small_regions_device(self, data, masks):
+        """The small-region stage (:332-380) of `_generate_general` on the device: holes and islands of all masks, their new areas
+        and boxes and the stage's box NMS in one enqueued chain (`ops.small_regions_select`), one download of the decision. The
+        kept records whose mask changed take the new box and area (:372-377); an unchanged mask equals its input, so the masks
+        are one gather of the chain's output."""
+        masks = masks.contiguous()
+        nm, table = ops.small_regions_select(masks, self.min_mask_region_area, max(self.box_nms_thresh, self.crop_nms_thresh))
+        keep, info, nb = ops.small_regions_table(table.cpu().numpy(), len(masks))   # the one download
+        changed = keep[(info[keep, 0] | info[keep, 1]) != 0]
+        data["boxes"][changed] = nb[changed]
+        data["area"][changed] = info[changed, 2]
+        return {k: v[keep] for k, v in data.items()}, nm[torch.from_numpy(keep).to(masks.device)]
+
     @torch.no_grad()
     def _generate_general(self, image):
         """-> (dict of host arrays, uint8 masks [m, H, W] on the device) over the final records."""
@@ -444,7 +496,9 @@ class SamAutomaticMaskGenerator:
             keep = nms_xyxy(data["boxes"], scores, self.crop_nms_thresh)
             data = {k: v[keep] for k, v in data.items()}
             masks = masks[torch.from_numpy(keep).to(dev)]
-        if self.min_mask_region_area > 0 and len(masks):                        # :332-380
+        if self.min_mask_region_area > 0 and len(masks) and self.amg_regions == "device":   # :332-380
+            data, masks = self._small_regions_device(data, masks)
+        elif self.min_mask_region_area > 0 and len(masks):
             cw = ops.CclWorkspace(H, W, 4096, dev)
             new_masks, scores = [], []
             for i in range(len(masks)):
