@@ -496,6 +496,39 @@ int psam_amg_select_crop(const int* stats, const float* iou4, const int* offsets
                          const int* orig_box, int* records, int cap, int* count, void* scratch, long long scratch_bytes,
                          void* stream);
 
+/* ---- crop layers of the automatic mask generator on the device (csrc/amg_crops.hip) ----------------------------------------------
+ * What lies between the per-crop selection (psam_amg_select_crop) and the image's final records, automatic_mask_generator.py:194-262,
+ * with nothing read back in between. Device tables, int32:
+ *   merged [pool_cap,11]: a psam_amg_select record with its box in the IMAGE's frame, then {crop index, pool row};
+ *   bases  [ncrops+1]   : bases[c] = merged records of the crops before c. Crop c's call reads bases[c] (0 for c = 0) and writes
+ *                         bases[c+1]; the calls of one image must be issued in crop order on one stream. No clearing needed.
+ *   geom   [ncrops,8]   : {x0, y0, crop width, crop height, ih, iw (predictor.input_size of the crop), bits of the float32 NMS score
+ *                         1 / crop area (utils/amg.py / automatic_mask_generator.py:208-213), 0}.
+ * psam_amg_keep_planes: records int32 [cap,9] and count int32 [1] as psam_amg_select_crop wrote them for crop `crop`, whose origin in
+ *   the image is (x0, y0); low fp32 [low_planes,IN,IN] the decoder's output that the records' plane indices refer to. The first
+ *   k = min(count, cap) records (count is read on the device; the launch is sized for cap) are appended to `merged` at rows bases[crop] ..,
+ *   box moved by (x0, y0), and each record's plane is copied to the same row of pool fp32 [pool_cap,IN,IN]. Rows >= pool_cap are written
+ *   nowhere; bases keeps counting, and psam_amg_crops_nms reports the overflow.
+ * psam_amg_crops_workspace: bytes of scratch psam_amg_crops_nms needs; host arithmetic only.
+ * psam_amg_crops_nms: cross-crop NMS of the bases[ncrops] merged records: psam_box_nms (its rule, its order among equal scores)
+ *   with every record scored by its crop's geom score; use_nms = 0 (a single crop box, :208) keeps all in merged order.
+ *   out int32 [pool_cap*11 + 2]: the final records in suppression order, then the final count (-1: bases[ncrops] > pool_cap, the pool
+ *   overflowed and nothing else of out is meaningful), then bases[ncrops]. One copy of out gives the host the whole decision.
+ * psam_mask_binarize_crops: out uint8 [m,H,W], every byte written: frame i is zero outside the rectangle of final record i's crop and
+ *   holds, inside it, the bits of psam_mask_binarize_resized of the record's pool plane with that crop's (ih, iw), crop size and
+ *   origin. One launch serves records of crops of different sizes. A record whose crop index, pool row or geometry is out of range
+ *   gives a zero frame.
+ * Status 1 before any launch: pool_cap outside 1 .. 16384 (the group limit of psam_box_nms), crop outside [0, ncrops), negative
+ * origin, cap < 1, IN*IN not a multiple of 4, low or pool not 16-byte aligned, m outside 1 .. pool_cap, variant outside 0 .. 2,
+ * a NaN threshold, a null pointer, scratch too small or misaligned (16 bytes). */
+int psam_amg_keep_planes(const float* low, int low_planes, int IN, const int* records, const int* count, int cap, int crop, int ncrops,
+                         int x0, int y0, float* pool, int pool_cap, int* merged, int* bases, void* stream);
+int psam_amg_crops_workspace(int pool_cap, long long* bytes);
+int psam_amg_crops_nms(const int* merged, const int* bases, int ncrops, const int* geom, int pool_cap, double thr, int use_nms,
+                       int* out, void* scratch, long long scratch_bytes, void* stream);
+int psam_mask_binarize_crops(const float* pool, int pool_cap, const int* final_records, int m, const int* geom, int ncrops, int IN,
+                             int MID, int variant, float thr, unsigned char* out, int H, int W, void* stream);
+
 /* ---- small-region removal for a batch of masks (csrc/small_regions.hip) --------------------------------------------------
  * Per mask, bit for bit remove_small_regions(mask, t, "holes") then remove_small_regions(., t, "islands")
  * (segment_anything/utils/amg.py:267-291; the stage of automatic_mask_generator.py:332-380), 8-connected:

@@ -99,6 +99,11 @@ SIGNATURES = {
                         c_void_p, c_int, c_void_p, c_void_p, c_longlong, c_void_p],
     "psam_amg_select_crop": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                              ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_void_p, c_int, c_void_p, c_void_p, c_longlong, c_void_p],
+    "psam_amg_keep_planes": [c_void_p, c_int, c_int, c_void_p, c_void_p] + [c_int] * 5 + [c_void_p, c_int, c_void_p, c_void_p, c_void_p],
+    "psam_amg_crops_workspace": [c_int, ctypes.POINTER(c_longlong)],
+    "psam_amg_crops_nms": [c_void_p, c_void_p, c_int, c_void_p, c_int, ctypes.c_double, c_int, c_void_p, c_void_p, c_longlong, c_void_p],
+    "psam_mask_binarize_crops": [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_int, c_int,
+                                 c_void_p],
     "psam_small_regions_workspace": [c_int, c_int, c_int, ctypes.POINTER(c_longlong)],
     "psam_small_regions": [c_void_p, c_int, c_int, c_int, ctypes.c_double, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                            c_longlong, c_void_p],

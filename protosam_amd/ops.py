@@ -1397,7 +1397,121 @@ def amg_select_crop(stats, iou4, offsets, pred_iou_thresh, stability_score_thres
                       scratch=scratch, _crop=(cb, ob))
 
 
-SMALL_REGIONS_BUDGET = 256 << 20    # bytes of scratch small_regions sizes its chunk for (8 bytes per pixel and mask in flight)
+AMG_CREC = 11           # int32 words of a merged / final crop record: an AMG_REC record (box in the image's frame), crop index, pool row
+AMG_GEOM = 8            # int32 words of a crop geometry row: x0, y0, crop width, crop height, ih, iw, float32 bits of 1 / crop area, 0
+_crops_scratch = {}
+
+
+def amg_crop_geometry(crop_boxes, in_sizes):
+    """The crop geometry table of the crops route, on the host: crop_boxes [ncrops] XYXY ints, in_sizes [ncrops] (ih, iw) =
+    predictor.input_size of every crop -> numpy int32 [ncrops, AMG_GEOM]. The score is the float32 1 / crop area of
+    SamAutomaticMaskGenerator._generate_general's cross-crop NMS, computed by its numpy expression."""
+    import numpy as np
+    cb = np.asarray(crop_boxes, dtype=np.int64).reshape(-1, 4)
+    ins = np.asarray(in_sizes, dtype=np.int64).reshape(-1, 2)
+    if len(ins) != len(cb):
+        raise ValueError(f"{len(cb)} crop boxes but {len(ins)} input sizes")
+    f = cb.astype(np.float32)
+    scores = (1.0 / ((f[:, 2] - f[:, 0]) * (f[:, 3] - f[:, 1]))).astype(np.float32)
+    g = np.zeros((len(cb), AMG_GEOM), np.int32)
+    g[:, 0], g[:, 1], g[:, 2], g[:, 3] = cb[:, 0], cb[:, 1], cb[:, 2] - cb[:, 0], cb[:, 3] - cb[:, 1]
+    g[:, 4:6] = ins
+    g[:, 6] = scores.view(np.int32)
+    return g
+
+
+def _pool_args(pool, merged, bases, ncrops):
+    _req(pool, torch.float32, "pool"); _req(merged, torch.int32, "merged"); _req(bases, torch.int32, "bases")
+    if pool.dim() != 3 or pool.shape[1] != pool.shape[2] or not pool.is_contiguous():
+        raise ValueError(f"pool: expected a contiguous [pool_cap, IN, IN], got {tuple(pool.shape)}")
+    pool_cap = pool.shape[0]
+    if not 1 <= pool_cap <= NMS_MAX_GROUP:
+        raise ValueError(f"a pool of {pool_cap} planes is outside 1 .. {NMS_MAX_GROUP}, the group limit of the cross-crop NMS")
+    if not merged.is_contiguous() or merged.numel() < pool_cap * AMG_CREC:
+        raise ValueError(f"merged: expected at least {pool_cap * AMG_CREC} contiguous words, got {merged.numel()}")
+    if not bases.is_contiguous() or bases.numel() < ncrops + 1 or ncrops < 1:
+        raise ValueError(f"bases: expected at least {ncrops + 1} contiguous words for {ncrops} crops, got {bases.numel()}")
+    return pool_cap
+
+
+def amg_keep_planes(low, records, count, crop, ncrops, origin, pool, merged, bases):
+    """After crop `crop`'s amg_select_crop (psam_amg_keep_planes): its first min(count, cap) records - records int32 [cap, AMG_REC],
+    count int32 [1], both on the device, nothing is read back - join `merged` int32 [pool_cap, AMG_CREC] at the rows that `bases`
+    int32 [ncrops + 1] counts, with the box moved by origin = (x0, y0) into the image's frame, and their planes of low
+    [n, 4, IN, IN] are copied into the same rows of pool fp32 [pool_cap, IN, IN]. The calls of one image go in crop order on one
+    stream. Rows past the pool are not written; amg_crops_nms reports that."""
+    _req(low, torch.float32, "low"); _req(records, torch.int32, "records"); _req(count, torch.int32, "count")
+    pool_cap = _pool_args(pool, merged, bases, ncrops)
+    IN = pool.shape[1]
+    if not low.is_contiguous() or low.shape[-1] != IN or low.shape[-2] != IN:
+        raise ValueError(f"low: expected contiguous planes of {IN} x {IN}, got {tuple(low.shape)}")
+    if records.dim() != 2 or records.shape[1] != AMG_REC or records.stride(1) != 1 or records.stride(0) != AMG_REC:
+        raise ValueError(f"records: expected a dense [cap, {AMG_REC}], got {tuple(records.shape)}")
+    cap = records.shape[0]
+    x0, y0 = (int(v) for v in origin)
+    st = _lib.lib().psam_amg_keep_planes(_ptr(low), low.numel() // (IN * IN), IN, _ptr(records), _ptr(count), cap, int(crop), int(ncrops),
+                                         x0, y0, _ptr(pool), pool_cap, _ptr(merged), _ptr(bases), _stream())
+    _lib.check(st, "psam_amg_keep_planes")
+
+
+def amg_crops_workspace(pool_cap):
+    """Bytes of scratch psam_amg_crops_nms needs for a pool of pool_cap planes."""
+    nbytes = _lib.c_longlong(0)
+    _lib.check(_lib.lib().psam_amg_crops_workspace(int(pool_cap), nbytes), "psam_amg_crops_workspace")
+    return nbytes.value
+
+
+def amg_crops_nms(merged, bases, geom, ncrops, pool_cap, iou_threshold, use_nms=True, out=None, scratch=None):
+    """Cross-crop NMS on the device (psam_amg_crops_nms) over the bases[ncrops] merged records, equal to utils.amg.nms_xyxy with
+    the float32 score 1 / crop area of every record's crop (geom int32 [ncrops, AMG_GEOM] on the device, amg_crop_geometry);
+    use_nms=False (a single crop box) keeps every record in merged order. -> out int32 [pool_cap * AMG_CREC + 2]: the final records
+    in suppression order, the final count (-1 where the pool overflowed) and the merged total; one copy of it is the decision."""
+    _req(merged, torch.int32, "merged"); _req(bases, torch.int32, "bases"); _req(geom, torch.int32, "geom")
+    pool_cap, ncrops = int(pool_cap), int(ncrops)
+    if not 1 <= pool_cap <= NMS_MAX_GROUP:
+        raise ValueError(f"a pool of {pool_cap} planes is outside 1 .. {NMS_MAX_GROUP}, the group limit of the cross-crop NMS")
+    assert merged.is_contiguous() and merged.numel() >= pool_cap * AMG_CREC and bases.is_contiguous() and bases.numel() >= ncrops + 1
+    assert geom.is_contiguous() and geom.numel() >= ncrops * AMG_GEOM and ncrops >= 1
+    words = pool_cap * AMG_CREC + 2
+    if out is None:
+        out = torch.empty((words,), dtype=torch.int32, device=merged.device)
+    _req(out, torch.int32, "out")
+    assert out.is_contiguous() and out.numel() >= words
+    if scratch is None:
+        key = (str(merged.device), pool_cap)
+        if key not in _crops_scratch:
+            _crops_scratch[key] = torch.empty((amg_crops_workspace(pool_cap) + 7) // 8, dtype=torch.int64, device=merged.device)
+        scratch = _crops_scratch[key]
+    if not scratch.is_cuda or scratch.dtype != torch.int64 or not scratch.is_contiguous():
+        raise TypeError("scratch: expected a contiguous int64 device tensor")
+    _req_aligned(scratch, 16, "scratch")
+    st = _lib.lib().psam_amg_crops_nms(_ptr(merged), _ptr(bases), ncrops, _ptr(geom), pool_cap, float(iou_threshold), 1 if use_nms else 0,
+                                       _ptr(out), _ptr(scratch), scratch.numel() * 8, _stream())
+    _lib.check(st, "psam_amg_crops_nms")
+    return out
+
+
+def mask_binarize_crops(pool, final_records, m, geom, ncrops, MID, size, variant, thr=0.0, out=None):
+    """The masks of the first m final records (psam_mask_binarize_crops): final_records int32 [>= m * AMG_CREC] on the device (the
+    `out` of amg_crops_nms), pool fp32 [pool_cap, IN, IN], geom int32 [ncrops, AMG_GEOM] -> uint8 [m, H, W] for size = (H, W): frame i
+    holds mask_binarize_resized of record i's pool plane with its crop's input size, crop size and origin, and is zero elsewhere."""
+    _req(pool, torch.float32, "pool"); _req(final_records, torch.int32, "final_records"); _req(geom, torch.int32, "geom")
+    assert pool.is_contiguous() and pool.dim() == 3 and final_records.is_contiguous() and geom.is_contiguous()
+    pool_cap, IN = pool.shape[0], pool.shape[1]
+    m, ncrops = int(m), int(ncrops)
+    H, W = (int(v) for v in size)
+    if not 1 <= m <= pool_cap or final_records.numel() < m * AMG_CREC or geom.numel() < ncrops * AMG_GEOM:
+        raise ValueError(f"mask_binarize_crops: {m} records of a pool of {pool_cap}, {final_records.numel()} record words")
+    if out is None:
+        out = torch.empty((m, H, W), dtype=torch.uint8, device=pool.device)
+    assert out.dtype == torch.uint8 and out.is_contiguous() and tuple(out.shape) == (m, H, W)
+    st = _lib.lib().psam_mask_binarize_crops(_ptr(pool), pool_cap, _ptr(final_records), m, _ptr(geom), ncrops, IN, MID, variant, float(thr),
+                                             _ptr(out), H, W, _stream())
+    _lib.check(st, "psam_mask_binarize_crops")
+    return out
+
+
+SMALL_REGIONS_BUDGET = 256 << 20   # bytes of scratch small_regions sizes its chunk for (8 bytes per pixel and mask in flight)
 _sr_scratch = {}
 
 

@@ -53,6 +53,10 @@ class SamWrapper(nn.Module):
         dev = self.sam.device
         lab = self._check_label(image, image_labels).to(device=dev, dtype=torch.uint8).contiguous()
         cand, masks, counts = self.mask_generator.generate_device(image, lab)   # :38
+        return self._best_mask(cand, masks, counts, return_device)
+
+    def _best_mask(self, cand, masks, counts, return_device):
+        """:40-48 over the proposals of `generate_device`: the mask with the largest IoU against the label; sets `last_stats`."""
         if masks.shape[0] == 0:
             raise TypeError("list indices must be integers or slices, not NoneType")   # masks[None], :48
         c = counts.cpu().numpy().astype(np.float64)
@@ -87,7 +91,8 @@ class SamWrapper(nn.Module):
         `psam_mask_counts` ({tp, fp, fn} of the survivors), `psam_best_iou`, and the binarisation of the one winning plane - and
         the decoder's output buffer is reused in stream order. The host waits once, after the last image; an image without a
         surviving proposal then raises `forward`'s TypeError. `last_stats` becomes a list with one `forward`-style dict per image.
-        A generator that is off the fused path (crop layers, small-region removal) runs `forward` image by image."""
+        A generator that is off the fused path (crop layers, small-region removal) goes through `generate_device_batch`: the crops'
+        device route per image, the host's wait for image i behind the crops of image i + 1, then `forward`'s choice."""
         from . import ops
         raw = list(images)
         images = [self.transform.apply_image(im) for im in raw]                 # :37
@@ -102,9 +107,12 @@ class SamWrapper(nn.Module):
             raise ValueError("forward_batch: all images of a batch must have the same size")
         g = self.mask_generator
         if not all(g._fast_path(im) for im in images):
+            # crop layers, small-region removal: `generate_device_batch` (the crops' device route, the host one image behind the
+            # device), then `forward`'s choice per image
+            labs_d = [lb.to(device=dev, dtype=torch.uint8).contiguous() for lb in labs]
             outs, stats = [], []
-            for im, lb in zip(raw, labs):
-                outs.append(self.forward(im, lb, return_device=return_device))
+            for cand, masks, counts in g.generate_device_batch(images, labs_d):
+                outs.append(self._best_mask(cand, masks, counts, return_device))
                 stats.append(self.last_stats)
             self.last_stats = stats
             return torch.stack(outs) if return_device else np.stack(outs)

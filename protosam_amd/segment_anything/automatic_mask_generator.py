@@ -39,7 +39,17 @@ download of the decision; the masks are then one gather. `PSAM_AMG_REGIONS=host`
 return the same records; profiles/amg_small_regions_bench.txt has the timings behind the default.
 With `PSAM_AMG_SELECT=device` a crop's candidates are selected on the device too (`psam_amg_select_crop`: `psam_amg_select` with
 the crop-edge filter of :309-311): one copy of the records instead of the statistics table, and the binarisation reads its planes
-from the record table. With the default, `host`, a crop is selected on the host as before. Cross-crop NMS stays on the host.
+from the record table. With the default, `host`, a crop is selected on the host as before.
+
+`PSAM_AMG_CROPS=device` (read in the constructor; default `host` for the single-image entry points, and what the batch entry points
+always do) takes the host out of the crop loop (csrc/amg_crops.hip): per crop encode, decode, statistics, `psam_amg_select_crop`
+and `psam_amg_keep_planes` - the crop's kept records join the image's merged table, translated to the image's frame, and their
+logit planes a plane pool, because the next crop overwrites the decoder's output - with nothing read back; behind the last crop
+`psam_amg_crops_nms` (cross-crop NMS on the device, `psam_box_nms` with the float32 1 / crop area scores of :208-213), ONE copy of
+the final records and one wait; then `psam_mask_binarize_crops` for the final records only, each with its own crop's geometry, and
+the small-region stage as before. Device memory is the pool (`crop_pool_cap` planes of 256 KiB, default 256 per crop) instead of
+(survivors of all crops) x H x W bytes; a pool overflow is reported in the final table and sends the image down the host route.
+The records are the host route's, record for record.
 
 `PSAM_AMG_RESIZE=materialise` (read in the constructor, default `fused`) selects the earlier route for any-size images and
 crops: the candidates that pass the predicted-IoU filter are written at full size in chunks of 64 (`postprocess_masks`) and
@@ -66,7 +76,7 @@ class SamAutomaticMaskGenerator:
                  stability_score_thresh=0.95, stability_score_offset=1.0, box_nms_thresh=0.7, crop_n_layers=0,
                  crop_nms_thresh=0.7, crop_overlap_ratio=512 / 1500, crop_n_points_downscale_factor=1,
                  point_grids=None, min_mask_region_area=0, output_mode="binary_mask", custom_points="false",
-                 decode_chunk=256):
+                 decode_chunk=256, crop_pool_cap=None):
         assert (points_per_side is None) != (point_grids is None), \
             "Exactly one of points_per_side or point_grid must be provided."
         if points_per_side is not None:
@@ -108,6 +118,16 @@ class SamAutomaticMaskGenerator:
         self.amg_regions = os.environ.get("PSAM_AMG_REGIONS", "device")
         if self.amg_regions not in ("host", "device"):
             raise ValueError(f"PSAM_AMG_REGIONS must be 'host' or 'device', got {self.amg_regions!r}")
+        # the general path's crops (crop_n_layers > 0, or the one crop of min_mask_region_area > 0): "host" (the default of the
+        # single-image entry points: the host waits for every crop, binarises every per-crop survivor into a full frame and runs
+        # the cross-crop NMS) or "device" (`_crops_enqueue` / `_crops_finish`: no wait per crop, cross-crop NMS on the device, one
+        # copy per image, only the final records binarised); the batch entry points always take the device route
+        self.amg_crops = os.environ.get("PSAM_AMG_CROPS", "host")
+        if self.amg_crops not in ("host", "device"):
+            raise ValueError(f"PSAM_AMG_CROPS must be 'host' or 'device', got {self.amg_crops!r}")
+        if crop_pool_cap is not None and not 1 <= int(crop_pool_cap) <= ops.NMS_MAX_GROUP:
+            raise ValueError(f"crop_pool_cap must be in 1 .. {ops.NMS_MAX_GROUP}, got {crop_pool_cap}")
+        self.crop_pool_cap = None if crop_pool_cap is None else int(crop_pool_cap)
         self._low = None
 
     def to(self, device):  # models/SamWrapper.py:52-54 calls this
@@ -347,6 +367,15 @@ class SamAutomaticMaskGenerator:
                     area=area[order], points=pts[kept[order] // 3] + np.array([[x0, y0]], dtype=np.float64),
                     crop_boxes=np.tile(np.array([crop_box], dtype=np.int64), (len(order), 1)), masks=full_masks)
 
+    def _crop_stats(self, in_size, crop_size):
+        """The int32 [3n, 8] statistics table of the crop whose logits are in self._low, straight from them (device)."""
+        sam = self.predictor.model
+        S, variant, thr = sam.image_encoder.img_size, sam.variant_id(), float(sam.mask_threshold)
+        if in_size == crop_size:
+            return ops.mask_stats(self._low, 1, 3, S, crop_size[0], crop_size[1], variant, thr, self.stability_score_offset)
+        return ops.mask_stats_resized(self._low, 1, 3, S, in_size, crop_size, variant, thr, self.stability_score_offset,
+                                      score=self._iou, score_thresh=self.pred_iou_thresh)
+
     def _crop_fused(self, pts, crop_box, in_size, orig_size):
         """`_process_crop` after the decoder, without a full-resolution candidate: one statistics table for all 3n candidates
         straight from the logits, one download, the host filters and NMS in `_process_crop`'s order, and only the NMS survivors
@@ -358,11 +387,7 @@ class SamAutomaticMaskGenerator:
         dev = self._low.device
         S, variant, thr = sam.image_encoder.img_size, sam.variant_id(), float(sam.mask_threshold)
         n = len(pts)
-        if in_size == (ch, cw):
-            stats = ops.mask_stats(self._low, 1, 3, S, ch, cw, variant, thr, self.stability_score_offset)
-        else:
-            stats = ops.mask_stats_resized(self._low, 1, 3, S, in_size, (ch, cw), variant, thr, self.stability_score_offset,
-                                           score=self._iou, score_thresh=self.pred_iou_thresh)
+        stats = self._crop_stats(in_size, (ch, cw))
         if self.amg_select == "device":
             return self._crop_select_device(stats, pts, crop_box, in_size, orig_size)
         host = torch.cat([stats.view(-1), self._iou.view(torch.int32).view(-1)]).cpu().numpy()   # the one download
@@ -415,6 +440,104 @@ class SamAutomaticMaskGenerator:
                     boxes=cand["boxes"] + np.array([[x0, y0, x0, y0]]), area=cand["area"],
                     points=cand["points"] + np.array([[x0, y0]], dtype=np.float64),
                     crop_boxes=np.tile(np.array([crop_box], dtype=np.int64), (k, 1)), masks=full_masks)
+
+    # ---- crops on the device (PSAM_AMG_CROPS=device, and always from the batch entry points) ----------------------------------
+    CROP_POOL_PER_CROP = 256
+
+    def _crops_device_ok(self):
+        """whether the general path can take the device route whatever PSAM_AMG_CROPS says (the batch entry points ask this):
+        PSAM_AMG_RESIZE=materialise and the per-mask host loop of PSAM_AMG_REGIONS=host keep today's route"""
+        return self.amg_resize == "fused" and not (self.min_mask_region_area > 0 and self.amg_regions == "host")
+
+    def _crop_pool_rows(self, caps):
+        """Rows of the plane pool (and of the merged table) for an image whose crops have `caps` candidates each: the constructor's
+        `crop_pool_cap`, or by default CROP_POOL_PER_CROP = 256 per crop (fewer where a crop has fewer candidates), shared by
+        all crops of the image, at most ops.NMS_MAX_GROUP - the group limit of the cross-crop NMS. A row is one 256 x 256 fp32
+        plane, 256 KiB: the default costs 64 MiB per crop - 320 MiB for the 5 crops of crop_n_layers=1, 1344 MiB for the 21 of
+        crop_n_layers=2 - and the batch entry points hold two pools. An image whose per-crop survivors do not fit is reported
+        by the device (`_crops_finish` returns None) and takes the host route."""
+        if self.crop_pool_cap is not None:
+            return self.crop_pool_cap
+        return max(1, min(ops.NMS_MAX_GROUP, sum(min(c, self.CROP_POOL_PER_CROP) for c in caps)))
+
+    def _crop_buffers(self, slot, pool_cap, ncrops, sel_words, dev):
+        """The device buffers of buffer set `slot`: pool, merged table, counter, final table, per-crop record table."""
+        sets = self.__dict__.setdefault("_crop_bufs", {})
+        b = sets.get(slot)
+        if b is None or b["key"][:3] != (pool_cap, ncrops, str(dev)) or b["key"][3] < sel_words:
+            b = sets[slot] = None                                               # (release before the new pool is made)
+            b = sets[slot] = dict(key=(pool_cap, ncrops, str(dev), sel_words),
+                                  pool=torch.empty((pool_cap, 256, 256), dtype=torch.float32, device=dev),
+                                  merged=torch.empty((pool_cap * ops.AMG_CREC,), dtype=torch.int32, device=dev),
+                                  bases=torch.empty((ncrops + 1,), dtype=torch.int32, device=dev),
+                                  out=torch.empty((pool_cap * ops.AMG_CREC + 2,), dtype=torch.int32, device=dev),
+                                  sel=torch.empty((sel_words,), dtype=torch.int32, device=dev))
+        return b
+
+    @torch.no_grad()
+    def _crops_enqueue(self, image, slot=0):
+        """Every crop of the image, enqueued with nothing read back: encode and decode by `_process_crop`'s calls (the same logits),
+        statistics, `psam_amg_select_crop`, `psam_amg_keep_planes` (the crop's records join the image's merged table, their planes
+        the pool); behind the last crop the geometry table goes up and `psam_amg_crops_nms` leaves the final records and their count
+        in ONE int32 device tensor, ctx["out"]. -> ctx for `_crops_finish`."""
+        pr = self.predictor
+        H, W = image.shape[:2]
+        crop_boxes, layer_idxs = generate_crop_boxes((H, W), self.crop_n_layers, self.crop_overlap_ratio)
+        ncrops = len(crop_boxes)
+        grids = [self.point_grids[li] for li in layer_idxs]
+        caps = [3 * len(g) for g in grids]
+        pool_cap = self._crop_pool_rows(caps)
+        dev = pr.device
+        buf = self._crop_buffers(slot, pool_cap, ncrops, max(caps) * ops.AMG_REC + 1, dev)
+        pts_all, in_sizes = [], []
+        for c, (crop_box, grid) in enumerate(zip(crop_boxes, grids)):
+            x0, y0, x1, y1 = crop_box
+            cropped = np.ascontiguousarray(image[y0:y1, x0:x1, :])
+            ch, cw = cropped.shape[:2]
+            pr.set_image(cropped)
+            pts = grid * np.array([[cw, ch]], dtype=np.float64)
+            self._decode_points(pts, (ch, cw))
+            in_size = tuple(int(v) for v in pr.input_size)
+            pr.reset_image()
+            stats = self._crop_stats(in_size, (ch, cw))
+            cap = caps[c]
+            records, count = ops.amg_select_crop(stats, self._iou, (0, cap), self.pred_iou_thresh, self.stability_score_thresh,
+                                                 self.box_nms_thresh, crop_box, [0, 0, W, H], cap=cap, out=buf["sel"])
+            ops.amg_keep_planes(self._low, records[0], count, c, ncrops, (x0, y0), buf["pool"], buf["merged"], buf["bases"])
+            pts_all.append(pts)
+            in_sizes.append(in_size)
+        geom = torch.from_numpy(ops.amg_crop_geometry(crop_boxes, in_sizes)).to(dev)          # the one upload
+        ops.amg_crops_nms(buf["merged"], buf["bases"], geom, ncrops, pool_cap, self.crop_nms_thresh, use_nms=ncrops > 1,   # :208
+                          out=buf["out"])
+        return dict(size=(H, W), crop_boxes=np.asarray(crop_boxes, dtype=np.int64), pts=pts_all, geom=geom, ncrops=ncrops,
+                    pool_cap=pool_cap, pool=buf["pool"], out=buf["out"])
+
+    @torch.no_grad()
+    def _crops_finish(self, ctx, table):
+        """`table`: the host copy (numpy int32) of ctx["out"]. -> (dict of host arrays, uint8 masks [m, H, W] on the device) over
+        the records that the cross-crop NMS left, as `_generate_general` has them in front of its small-region stage - only these
+        are binarised (`psam_mask_binarize_crops`, every record with its own crop's geometry). None where the pool overflowed."""
+        sam = self.predictor.model
+        H, W = ctx["size"]
+        words = ctx["pool_cap"] * ops.AMG_CREC
+        m = int(table[words])
+        if m < 0:
+            return None
+        r = table[:m * ops.AMG_CREC].reshape(m, ops.AMG_CREC).copy()           # (the caller may reuse `table`)
+        crop, cand = r[:, ops.AMG_REC].astype(np.int64), r[:, 0].astype(np.int64)
+        cb = ctx["crop_boxes"]
+        points = np.zeros((m, 2), np.float64)
+        for c in np.unique(crop):
+            sel = crop == c
+            points[sel] = ctx["pts"][c][cand[sel] // 3] + np.array([[cb[c, 0], cb[c, 1]]], dtype=np.float64)
+        data = dict(iou_preds=np.ascontiguousarray(r[:, 2]).view(np.float32), stability_score=np.ascontiguousarray(r[:, 3]).view(np.float32),
+                    boxes=r[:, 5:9].astype(np.int64), area=np.ascontiguousarray(r[:, 4]), points=points, crop_boxes=cb[crop])
+        dev = ctx["pool"].device
+        if m == 0:
+            return data, torch.empty((0, H, W), dtype=torch.uint8, device=dev)
+        masks = ops.mask_binarize_crops(ctx["pool"], ctx["out"], m, ctx["geom"], ctx["ncrops"], sam.image_encoder.img_size, (H, W),
+                                        sam.variant_id(), float(sam.mask_threshold))
+        return data, masks
 
     def _zero_plane(self, H, W, dev):
         z = getattr(self, "_zero_planes", None)
@@ -484,6 +607,16 @@ class SamAutomaticMaskGenerator:
     @torch.no_grad()
     def _generate_general(self, image):
         """-> (dict of host arrays, uint8 masks [m, H, W] on the device) over the final records."""
+        if self.amg_crops == "device" and self.amg_resize == "fused":
+            ctx = self._crops_enqueue(image)
+            done = self._crops_finish(ctx, ctx["out"].cpu().numpy())           # the image's one copy and wait
+            if done is not None:
+                return self._small_region_stage(*done)
+        return self._small_region_stage(*self._crops_host(image))              # PSAM_AMG_CROPS=host, or the pool overflowed
+
+    def _crops_host(self, image):
+        """The crops of the general path with the host between them (PSAM_AMG_CROPS=host): every crop waits for its statistics or
+        its records, its survivors are binarised into full frames, and the cross-crop NMS runs on the host."""
         H, W = image.shape[:2]
         crop_boxes, layer_idxs = generate_crop_boxes((H, W), self.crop_n_layers, self.crop_overlap_ratio)
         parts = [self._process_crop(image, cb, li, (H, W)) for cb, li in zip(crop_boxes, layer_idxs)]
@@ -496,6 +629,12 @@ class SamAutomaticMaskGenerator:
             keep = nms_xyxy(data["boxes"], scores, self.crop_nms_thresh)
             data = {k: v[keep] for k, v in data.items()}
             masks = masks[torch.from_numpy(keep).to(dev)]
+        return data, masks
+
+    def _small_region_stage(self, data, masks):
+        """:332-380 behind the crops of either route; without min_mask_region_area > 0 it hands its arguments back."""
+        H, W = masks.shape[1:]
+        dev = masks.device
         if self.min_mask_region_area > 0 and len(masks) and self.amg_regions == "device":   # :332-380
             data, masks = self._small_regions_device(data, masks)
         elif self.min_mask_region_area > 0 and len(masks):
@@ -540,23 +679,37 @@ class SamAutomaticMaskGenerator:
         pycocotools at construction as in the reference; `utils.amg.coco_encode_rle(rec["segmentation"])` on the
         "uncompressed_rle" records gives the same COCO record without the package)."""
         if not self._fused_path(image):
-            data, masks = self._generate_general(image)
-            masks = self._segmentations(masks)
-            anns = []
-            for i in range(len(masks)):
-                anns.append({
-                    "segmentation": masks[i],
-                    "area": int(data["area"][i]),
-                    "bbox": box_xyxy_to_xywh(data["boxes"][i]).tolist(),
-                    "predicted_iou": float(data["iou_preds"][i]),
-                    "point_coords": [data["points"][i].tolist()],
-                    "stability_score": float(data["stability_score"][i]),
-                    "crop_box": box_xyxy_to_xywh(data["crop_boxes"][i]).tolist(),
-                })
-            return anns
+            return self._general_records(*self._generate_general(image))
         cand = self._candidates(image)
         masks, _ = self._binarize(cand)
         return self._fused_records(cand, masks)
+
+    def _general_records(self, data, masks):
+        """The records of the general path from `_generate_general`'s host arrays and uint8 device masks."""
+        masks = self._segmentations(masks)
+        anns = []
+        for i in range(len(masks)):
+            anns.append({
+                "segmentation": masks[i],
+                "area": int(data["area"][i]),
+                "bbox": box_xyxy_to_xywh(data["boxes"][i]).tolist(),
+                "predicted_iou": float(data["iou_preds"][i]),
+                "point_coords": [data["points"][i].tolist()],
+                "stability_score": float(data["stability_score"][i]),
+                "crop_box": box_xyxy_to_xywh(data["crop_boxes"][i]).tolist(),
+            })
+        return anns
+
+    @staticmethod
+    def _general_device(data, masks, label, size):
+        """`generate_device`'s triple for the general path: {tp, fp, fn} of every record against the label
+        (models/SamWrapper.py:8-13), on the device."""
+        counts = None
+        if label is not None:
+            lab = (label != 0)
+            m = masks != 0
+            counts = torch.stack([(m & lab).flatten(1).sum(1), (m & ~lab).flatten(1).sum(1), (~m & lab).flatten(1).sum(1)], 1)
+        return dict(data, size=tuple(size)), masks, counts
 
     def _fused_records(self, cand, masks):
         """The records of the fused path from its candidate dict and the kept candidates' uint8 device masks."""
@@ -575,28 +728,55 @@ class SamAutomaticMaskGenerator:
             })
         return anns
 
-    def _pipelined(self, images, finish, fallback):
+    def _pipelined(self, images, finish, finish_general, fallback):
         """The fused path over several images with the host one image behind the device: image i's encode, decode, statistics and
         selection (`psam_amg_select`) are enqueued into buffer pair i % 2, its record table is copied to pinned memory behind an
         event, and the host waits for that event only after image i + 1 has been enqueued; then `finish(i, cand, low)` enqueues
         what works on the survivors. Every image is encoded and decoded by the calls `generate` makes, so its logits are the same
-        bits. Images off the fused path go to `fallback(i)` one by one, after what is pending."""
+        bits. An image on the general path (crop layers, small-region removal) takes the crops' device route in the same way: all
+        its crops are enqueued (`_crops_enqueue`, buffer set i % 2: the planes it needs later are in that set's pool, not in the
+        decoder's output), its final table is copied to pinned memory behind an event, and after the wait
+        `finish_general(i, data, masks)` gets what `_generate_general` returns. What that route does not cover
+        (`_crops_device_ok`) goes to `fallback(i)`, one by one, after what is pending; an image whose plane pool overflowed takes
+        the host route (`_crops_host`) after the last image."""
         out = [None] * len(images)
         pending = None
 
         def drain():
             nonlocal pending
-            if pending is not None:
-                i, ctx, records, host, ev = pending
-                pending = None
-                ev.synchronize()
+            if pending is None:
+                return
+            i, ctx, records, host, ev = pending
+            pending = None
+            ev.synchronize()
+            if records is not None:
                 out[i] = finish(i, self._cand_from_records(ctx, host.numpy(), records), ctx["low"])
+                return
+            done = self._crops_finish(ctx, host.numpy())
+            if done is None:
+                overflowed.append(i)            # (after the loop: the host route writes self._low, which image i + 1 may still need)
+            else:
+                out[i] = finish_general(i, *self._small_region_stage(*done))
+
+        overflowed = []
 
         k = 0
         for i, image in enumerate(images):
             if not self._fused_path(image):
-                drain()
-                out[i] = fallback(i)
+                if not self._crops_device_ok():
+                    drain()
+                    out[i] = fallback(i)
+                    continue
+                if pending is not None and pending[2] is not None:
+                    drain()                                                     # a pending fused image still needs self._low
+                ctx = self._crops_enqueue(image, slot=k % 2)
+                host = self._pinned(ctx["out"].numel(), k % 2)
+                host.copy_(ctx["out"], non_blocking=True)
+                ev = torch.cuda.Event()
+                ev.record()
+                drain()                                                         # image i - 1, while image i's crops run
+                pending = (i, ctx, None, host, ev)
+                k += 1
                 continue
             ctx = self._enqueue(image, slot=k % 2)
             dev_out, records, _ = self._select_enqueue(ctx, out=self._select_out(ctx, k % 2))
@@ -608,6 +788,8 @@ class SamAutomaticMaskGenerator:
             pending = (i, ctx, records, host, ev)
             k += 1
         drain()
+        for i in overflowed:
+            out[i] = finish_general(i, *self._small_region_stage(*self._crops_host(images[i])))
         return out
 
     def _select_out(self, ctx, slot):
@@ -629,11 +811,13 @@ class SamAutomaticMaskGenerator:
     @torch.no_grad()
     def generate_batch(self, images):
         """`[generate(im) for im in images]`, the same records, with the candidate selection on the device and the host's wait
-        for image i behind the enqueue of image i + 1 (see `_pipelined`). Images that take the general path are handled by
-        `generate` one by one."""
+        for image i behind the enqueue of image i + 1 (see `_pipelined`). Images on the general path (crop layers, small-region
+        removal) take the crops' device route, whatever PSAM_AMG_CROPS says, with one wait per image behind the next image's crops;
+        only PSAM_AMG_RESIZE=materialise, min_mask_region_area > 0 with PSAM_AMG_REGIONS=host, and an image whose plane pool
+        overflowed are handled by the single-image host route, one by one."""
         images = list(images)
         return self._pipelined(images, lambda i, cand, low: self._fused_records(cand, self._binarize(cand, low=low)[0]),
-                               lambda i: self.generate(images[i]))
+                               lambda i, data, masks: self._general_records(data, masks), lambda i: self.generate(images[i]))
 
     @torch.no_grad()
     def generate_device_batch(self, images, labels=None):
@@ -644,6 +828,7 @@ class SamAutomaticMaskGenerator:
         if len(labels) != len(images):
             raise ValueError(f"{len(images)} images but {len(labels)} labels")
         return self._pipelined(images, lambda i, cand, low: (cand,) + tuple(self._binarize(cand, labels[i], low=low)),
+                               lambda i, data, masks: self._general_device(data, masks, labels[i], images[i].shape[:2]),
                                lambda i: self.generate_device(images[i], labels[i]))
 
     @torch.no_grad()
@@ -651,14 +836,7 @@ class SamAutomaticMaskGenerator:
         """Device-resident variant for callers that reduce the masks further: -> (candidate dict, uint8 masks [n,H,W] on
         the device, int64 [n,3] {tp, fp, fn} against `label` or None)."""
         if not self._fused_path(image):
-            data, masks = self._generate_general(image)
-            counts = None
-            if label is not None:   # {tp, fp, fn} of every record against the label (models/SamWrapper.py:8-13), on the device
-                lab = (label != 0)
-                m = masks != 0
-                counts = torch.stack([(m & lab).flatten(1).sum(1), (m & ~lab).flatten(1).sum(1), (~m & lab).flatten(1).sum(1)], 1)
-            data = dict(data, size=tuple(image.shape[:2]))
-            return data, masks, counts
+            return self._general_device(*self._generate_general(image), label, image.shape[:2])
         cand = self._candidates(image)
         masks, counts = self._binarize(cand, label)
         return cand, masks, counts
