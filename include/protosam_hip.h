@@ -423,6 +423,38 @@ int psam_seg_counts(const void* pred, int pred_dtype, int pred_planes, long long
                     int label_dtype, int label_planes, long long label_stride, int H, int W, const int* rows, int n,
                     long long* out, void* stream);
 
+/* Surface-distance metrics (csrc/surface.hip): Hausdorff distance, its 95th percentile and the average (symmetric) surface
+ * distance of n (prediction, ground truth) pairs, MedPy's hd / hd95 / asd / assd with connectivity=1.
+ * rows int32 [n,5] = (first pred plane, pred value, first label plane, label value, depth D): the row covers D consecutive planes
+ * of each tensor; comparisons, dtypes and strides as psam_seg_counts. The surface of a set is its voxels with a face neighbour
+ * (4 in the plane for D == 1, 6 for D > 1) that is not in the set or lies outside the row's D x H x W range. Segment 2r is the
+ * prediction's surface of row r, segment 2r + 1 the ground truth's.
+ * psam_surface_points: counts int32 [2n] = the true surface sizes; offsets int32 [2n+1] = their exclusive scan (saturated at
+ *   INT_MAX); status int32 [n]: 0 filled, 1 the row's segments end beyond cap (not filled; an empty row always fits), 2 the row
+ *   is outside the planes or its depth outside 1 .. max_depth (nothing read, counts 0); points int32 [cap]: a surface voxel as
+ *   its index (z * H + y) * W + x in the row's range, in no particular order inside a segment; tiles int32 [2n+1] and cursors
+ *   int32 [2n] are work tables (tiles: the scan of the distance tiles, read by psam_surface_dist).
+ * psam_surface_dist: d2 fp32 [cap]: for every filled point the minimum over the other segment of its row of
+ *   ((dx*sx)*(dx*sx) + (dy*sy)*(dy*sy)) + (dz*sz)*(dz*sz), each operation a separately rounded fp32 one on exact integer offsets and
+ *   the spacing rounded to fp32; +inf where the other segment is empty. keys (may be null) int64 [cap]: segment << 32 | bits of d2,
+ *   so that ONE ascending sort of keys sorts every segment in place. Positions that are not filled are not written.
+ *   The grid is cap / 256 + 2n workgroups whatever the counts are; max_depth == 1 takes the two-term form.
+ * psam_surface_stats: sorted = the d2 of every segment ascending, element i at 4 * stride bytes * i (stride 1: the fp32 array,
+ *   2: the low words of sorted keys). out float64 [n,8] = {n_pred, n_gt, hd, hd95, assd, asd_pg, asd_gp, status}: hd the larger
+ *   directed maximum, hd95 numpy.percentile(., 95) of both directed sets together, asd_pg / asd_gp the directed means (prediction
+ *   to ground truth and back), assd their mean; all of sqrt((double)d2), summed in a fixed order: the same bits run to run and for
+ *   every cap that fits. The five are NaN where a surface is empty or status != 0.
+ * Status 1 before any launch: a null pointer, n < 1, cap outside 1 .. 2^31 - 2, H, W or max_depth outside 1 .. 2^24,
+ * max_depth * H * W > 2^31 - 4097, a spacing that is not positive and finite as fp32, stride not 1 or 2. */
+int psam_surface_points(const void* pred, int pred_dtype, int pred_planes, long long pred_stride, const void* label,
+                        int label_dtype, int label_planes, long long label_stride, int H, int W, int max_depth, const int* rows,
+                        int n, int* counts, int* offsets, int* tiles, int* status, int* cursors, int* points, int cap,
+                        void* stream);
+int psam_surface_dist(const int* points, const int* offsets, const int* tiles, int n, int H, int W, int max_depth, double sz,
+                      double sy, double sx, int cap, float* d2, long long* keys, void* stream);
+int psam_surface_stats(const void* sorted, int stride, const int* counts, const int* offsets, const int* status, int n,
+                       double* out, void* stream);
+
 /* PromptEncoder.mask_downscaling for mask prompts: masks fp32 [n,4g,4g] -> dense embeddings fp32 token-major [n,g*g,256].
  * wts = c1w[4][4] c1b[4] n1w[4] n1b[4] c2w[16][4][2][2] c2b[16] n2w[16] n2b[16] c3w[256][16] c3b[256] (4684 floats).
  * prompt_encoder.py:51-59,102-105; common.py:31-43 (LayerNorm2d) */

@@ -117,6 +117,11 @@ SIGNATURES = {
     "psam_rle_decode": [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p],
     "psam_seg_counts": [c_void_p, c_int, c_int, c_longlong, c_void_p, c_int, c_int, c_longlong, c_int, c_int, c_void_p, c_int,
                         c_void_p, c_void_p],
+    "psam_surface_points": [c_void_p, c_int, c_int, c_longlong, c_void_p, c_int, c_int, c_longlong, c_int, c_int, c_int, c_void_p,
+                            c_int] + [c_void_p] * 6 + [c_int, c_void_p],
+    "psam_surface_dist": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, ctypes.c_double, ctypes.c_double,
+                          ctypes.c_double, c_int, c_void_p, c_void_p, c_void_p],
+    "psam_surface_stats": [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p],
     "psam_mask_binarize": [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p,
                            c_void_p, c_void_p],
     "psam_mask_stats_resized": [c_void_p] + [c_int] * 11 + [c_float, c_float, c_void_p, c_void_p],

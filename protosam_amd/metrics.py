@@ -304,3 +304,87 @@ class Metric:
 
         cls = self._per_scan(lambda tp, fp, fn: two(tp) / (two(tp) + two(fp) + two(fn)), n_scan)
         return self._spread(cls) if n_scan is None else (cls, cls.mean())
+
+
+# ---- boundary measures from the table of ops.surface_distances ----------------------------------------------------------------------
+# HD, HD95 and ASSD as MedPy's hd / hd95 / asd / assd with connectivity=1 define them (restated in ops.surface_points /
+# surface_dist / surface_stats and DESIGN.md section 4b): surfaces by face neighbours with the array's edge as background,
+# Euclidean distances with voxel spacing, hd the larger directed maximum, hd95 numpy.percentile(., 95) of both directed sets
+# together, assd the mean of the two directed means; NaN, with the counts saying which side, where a surface is empty.
+
+N_PRED, N_GT, HD, HD95, ASSD, ASD_PG, ASD_GP, SURF_STATUS = range(8)
+
+
+def surface_rows(n, classes=None, label_planes=None, depth=1, pred_value=1, label_value=1):
+    """The row table of ops.surface_distances -> int32 array [rows, 5] of (first pred plane, pred value, first label plane, label
+    value, depth). It mirrors `class_rows`.
+    depth = 1, n slices: classes = [organ ids]: masks [n, C, H, W] against a label map, row k*C + c = (k*C + c, pred_value, label
+    plane of slice k, classes[c], 1); classes = None: masks [n, H, W], row k = (k, pred_value, label plane of slice k, label_value,
+    1). label_planes as in class_rows.
+    depth = D > 1, n volumes of D consecutive planes each (a scan): classes = [organ ids]: masks [n * C, D, H, W] (class-major
+    volumes), row k*C + c = ((k*C + c) * D, pred_value, first label plane of volume k, classes[c], D); classes = None: row k =
+    (k * D, pred_value, first label plane of volume k, label_value, D). label_planes: the FIRST label plane of every volume
+    (default k * D)."""
+    D = int(depth)
+    if D < 1:
+        raise ValueError(f"depth must be at least 1, got {depth}")
+    lp = [k * D for k in range(n)] if label_planes is None else [int(z) for z in label_planes]
+    if len(lp) != n:
+        raise ValueError(f"label_planes has {len(lp)} entries for {n} slices")
+    if classes is None:
+        return np.array([(k * D, pred_value, lp[k], label_value, D) for k in range(n)], dtype=np.int32).reshape(-1, 5)
+    C = len(classes)
+    return np.array([((k * C + c) * D, pred_value, lp[k], int(classes[c]), D) for k in range(n) for c in range(C)],
+                    dtype=np.int32).reshape(-1, 5)
+
+
+def score_surfaces(table, cases=None):
+    """Host half of the boundary measures (float64, no device): table [n, 8] as ops.surface_distances leaves it (ops.SURF_COLS).
+    A row counts when both of its surfaces are present and it was filled (status 0). -> dict: rows (indices that count), hd /
+    hd95 / assd / asd_pg / asd_gp (arrays over them), mean_hd / mean_hd95 / mean_assd (NaN without rows), n_pred / n_gt (surface
+    sizes of ALL rows), and the rows left out, each under a key of its own: empty_pred, empty_gt (a row with both surfaces empty
+    is in both), overflowed (status 1: the pool was too small, see `surface_table`), bad_rows (status 2). cases: per row the case
+    it belongs to -> hd95_cases / assd_cases {case: mean over its counted rows}."""
+    t = np.asarray(_host_table(table), dtype=np.float64).reshape(-1, 8)
+    status = t[:, SURF_STATUS].astype(np.int64)
+    n_pred, n_gt = t[:, N_PRED].astype(np.int64), t[:, N_GT].astype(np.int64)
+    ok = status == 0
+    kept = [int(k) for k in np.nonzero(ok & (n_pred > 0) & (n_gt > 0))[0]]
+    out = {"rows": kept, "n_pred": n_pred, "n_gt": n_gt,
+           "empty_pred": [int(k) for k in np.nonzero(ok & (n_pred == 0))[0]],
+           "empty_gt": [int(k) for k in np.nonzero(ok & (n_gt == 0))[0]],
+           "overflowed": [int(k) for k in np.nonzero(status == 1)[0]],
+           "bad_rows": [int(k) for k in np.nonzero(status > 1)[0]]}
+    for name, col in (("hd", HD), ("hd95", HD95), ("assd", ASSD), ("asd_pg", ASD_PG), ("asd_gp", ASD_GP)):
+        out[name] = t[kept, col] if kept else np.zeros(0, dtype=np.float64)
+    for name in ("hd", "hd95", "assd"):
+        out["mean_" + name] = float(np.mean(out[name])) if kept else float("nan")
+    by_case = {}
+    if cases is not None:
+        for i, k in enumerate(kept):
+            by_case.setdefault(cases[k], ([], []))
+            by_case[cases[k]][0].append(out["hd95"][i])
+            by_case[cases[k]][1].append(out["assd"][i])
+    out["hd95_cases"] = {c: float(np.mean(v[0])) for c, v in by_case.items()}
+    out["assd_cases"] = {c: float(np.mean(v[1])) for c, v in by_case.items()}
+    return out
+
+
+def surface_table(pred, label, rows, spacing=(1.0, 1.0, 1.0), cap=None, table=None):
+    """The complete host table [n, 8] of ops.surface_distances(pred, label, rows, spacing, cap): rows flagged as overflowed
+    (status 1) are computed again, only they, in one further call whose capacity is the sum of their true surface sizes (which
+    the first pass counted whatever its cap), so every row is as an un-overflowed run gives it, bit for bit. table: a table
+    already computed for these arguments (device or host) - then only the flagged rows run. rows: a list / array [n, 5]. It
+    synchronises (one copy per pass)."""
+    from . import ops
+    r = np.asarray(rows, dtype=np.int64).reshape(-1, 5)
+    host = np.array(_host_table(ops.surface_distances(pred, label, r.tolist(), spacing, cap=cap) if table is None else table),
+                    dtype=np.float64).reshape(-1, 8)
+    if host.shape[0] != r.shape[0]:
+        raise ValueError(f"table has {host.shape[0]} rows for {r.shape[0]} rows")
+    again = np.nonzero(host[:, SURF_STATUS] == 1)[0]
+    if again.size:
+        need = int(host[again, N_PRED].sum() + host[again, N_GT].sum())
+        host[again] = _host_table(ops.surface_distances(pred, label, r[again].tolist(), spacing, cap=max(need, 1)))
+        assert (host[again, SURF_STATUS] == 0).all()
+    return host

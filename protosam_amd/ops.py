@@ -1774,6 +1774,182 @@ def seg_counts(pred, label, rows, out=None):
     return out
 
 
+# ---- surface distances: HD, HD95, ASSD (csrc/surface.hip) ---------------------------------------------------
+SURFACE_TILE = 256                   # query points per workgroup and points per LDS tile of psam_surface_dist (SURF_TILE)
+SURF_COLS = ("n_pred", "n_gt", "hd", "hd95", "assd", "asd_pg", "asd_gp", "status")
+SURFACE_OK, SURFACE_OVERFLOW, SURFACE_BAD_ROW = 0, 1, 2         # the status column
+SURFACE_CAP_FLOOR, SURFACE_CAP_DIVISOR = 65536, 8
+_SURFACE_MAX_VOXELS = 0x7fffffff - 4096
+_SURFACE_MAX_SIDE = 1 << 24
+
+
+def _surface_spacing(spacing):
+    """(sz, sy, sx) as floats; a pair is (sy, sx) of a slice. ValueError unless every one is positive and finite as float32."""
+    import numpy as np
+    sp = tuple(float(v) for v in spacing)
+    if len(sp) == 2:
+        sp = (1.0,) + sp
+    if len(sp) != 3:
+        raise ValueError(f"spacing: expected (sz, sy, sx) or (sy, sx), got {spacing!r}")
+    with np.errstate(over="ignore"):
+        f = np.asarray(sp, dtype=np.float64).astype(np.float32)
+    if not (np.isfinite(f).all() and (f > 0).all()):
+        raise ValueError(f"spacing: every value must be positive and finite in float32, got {spacing!r}")
+    return sp
+
+
+def _surface_geometry(H, W, max_depth):
+    if H < 1 or W < 1 or max_depth < 1:
+        raise ValueError(f"surface: planes {H} x {W} and depth {max_depth} must be at least 1")
+    if max(H, W, max_depth) > _SURFACE_MAX_SIDE or max_depth * H * W > _SURFACE_MAX_VOXELS:
+        raise ValueError(f"surface: a row of {max_depth} x {H} x {W} voxels is outside int32 indexing (at most 2^31 - 4097 voxels, "
+                         f"2^24 a side)")
+
+
+def _surface_rows(rows, n_pred, n_lab, max_depth, device):
+    """rows as a list / array [n, 5] (range-checked, ValueError) or an int32 device tensor (then max_depth must be given).
+    -> (int32 device tensor, n, max_depth, list of depths or None)"""
+    if isinstance(rows, torch.Tensor):
+        _req(rows, torch.int32, "rows")
+        if rows.dim() != 2 or rows.shape[1] != 5 or not rows.is_contiguous() or rows.shape[0] < 1:
+            raise ValueError(f"rows: expected a contiguous int32 [n >= 1, 5] table, got {tuple(rows.shape)}")
+        if max_depth is None:
+            raise ValueError("rows on the device: max_depth= must be given (the launch is sized from it)")
+        return rows, rows.shape[0], int(max_depth), None
+    import numpy as np
+    r = np.asarray(rows, dtype=np.int64)
+    if r.size == 0 or r.ndim != 2 or r.shape[1] != 5:
+        raise ValueError(f"rows: expected [n >= 1, 5] = (pred plane, pred value, label plane, label value, depth), got {r.shape}")
+    for k, (pp, _, lp, _, D) in enumerate(r.tolist()):
+        if D < 1:
+            raise ValueError(f"rows[{k}]: depth {D} < 1")
+        if not (0 <= pp and pp + D <= n_pred):
+            raise ValueError(f"rows[{k}]: prediction planes {pp} .. {pp + D - 1} outside [0, {n_pred})")
+        if not (0 <= lp and lp + D <= n_lab):
+            raise ValueError(f"rows[{k}]: label planes {lp} .. {lp + D - 1} outside [0, {n_lab})")
+    if (np.abs(r) > 0x7fffffff).any():
+        raise ValueError("rows: a value does not fit int32")
+    depths = r[:, 4].tolist()
+    md = max(depths) if max_depth is None else int(max_depth)
+    if md < max(depths):
+        raise ValueError(f"max_depth {md} is below the deepest row ({max(depths)})")
+    return torch.from_numpy(r.astype(np.int32)).to(device), r.shape[0], md, depths
+
+
+def surface_default_cap(covered_voxels):
+    """The default pool size of surface_distances: an eighth of the voxels the rows cover (a closed surface of a region of v voxels
+    has far fewer than v / 8 voxels once the region is more than a few voxels thick, and a row holds two surfaces), at least 65536
+    points. A row that does not fit is flagged, never truncated."""
+    return int(min(max(SURFACE_CAP_FLOOR, int(covered_voxels) // SURFACE_CAP_DIVISOR), 0x7ffffffe))
+
+
+def surface_workspace(n, cap):
+    """Bytes of device memory one surface_distances call over n rows with a pool of cap points allocates: the work tables
+    (9n + 2 int32), points and d2 (4 bytes a point each), the sort keys and the sorted keys with the sort's index output
+    (8 bytes a point each), and the table [n, 8] float64. torch.sort's own temporaries are not counted."""
+    return 4 * (9 * n + 2) + cap * (4 + 4 + 8 + 8 + 8) + 64 * n
+
+
+def surface_points(pred, label, rows, cap, max_depth=None):
+    """Surface voxels of both sides of every row, compacted into one pool (psam_surface_points).
+    pred / label as seg_counts; rows [n, 5] = (first pred plane, pred value, first label plane, label value, depth D): the row
+    compares D consecutive planes of each. The surface of a set: its voxels with a face neighbour (4 in the plane for D == 1,
+    6 for D > 1) that is not in the set or lies outside the row's D x H x W range (scipy: M ^ binary_erosion(M, cross)).
+    -> dict `work`: counts int32 [n, 2] (the true sizes of S(pred), S(label), whatever cap is), offsets int32 [2n + 1] (their
+    exclusive scan: segment 2r = S(pred) of row r, 2r + 1 = S(label)), status int32 [n] (SURFACE_OK / SURFACE_OVERFLOW: the row's
+    segments end beyond cap and are not filled / SURFACE_BAD_ROW: a device row outside the planes), points int32 [cap] (linear
+    index (z * H + y) * W + x in the row's range; any order inside a segment), and the geometry. Asynchronous."""
+    if tuple(pred.shape[-2:]) != tuple(label.shape[-2:]):
+        raise ValueError(f"pred planes {tuple(pred.shape[-2:])} and label planes {tuple(label.shape[-2:])} differ")
+    if pred.dim() not in (3, 4) or label.dim() not in (3, 4):
+        raise ValueError(f"expected [planes, H, W] or [n, C, H, W], got {tuple(pred.shape)} and {tuple(label.shape)}")
+    import numpy as np
+    n_pred, n_lab = int(np.prod(pred.shape[:-2])), int(np.prod(label.shape[:-2]))
+    if not (pred.is_cuda and label.is_cuda):
+        raise RuntimeError("surface_points: expected device tensors (protosam_amd has no CPU path)")
+    rows, n, md, _ = _surface_rows(rows, n_pred, n_lab, max_depth, pred.device)
+    H, W = (int(v) for v in pred.shape[-2:])
+    _surface_geometry(H, W, md)
+    cap = int(cap)
+    if not 1 <= cap <= 0x7ffffffe:
+        raise ValueError(f"cap must be in 1 .. 2^31 - 2, got {cap}")
+    pred, n_pred, s_pred, _, _ = _seg_planes(pred, "pred")
+    label, n_lab, s_lab, _, _ = _seg_planes(label, "label")
+    tab = torch.empty(9 * n + 2, dtype=torch.int32, device=pred.device)
+    work = {"counts": tab[:2 * n].view(n, 2), "offsets": tab[2 * n:4 * n + 1], "tiles": tab[4 * n + 1:6 * n + 2],
+            "status": tab[6 * n + 2:7 * n + 2], "cursors": tab[7 * n + 2:],
+            "points": torch.empty(cap, dtype=torch.int32, device=pred.device),
+            "n": n, "H": H, "W": W, "max_depth": md, "cap": cap}
+    st = _lib.lib().psam_surface_points(_ptr(pred), _SEG_DT[pred.dtype], n_pred, s_pred, _ptr(label), _SEG_DT[label.dtype], n_lab,
+                                       s_lab, H, W, md, _ptr(rows), n, _ptr(work["counts"]), _ptr(work["offsets"]),
+                                       _ptr(work["tiles"]), _ptr(work["status"]), _ptr(work["cursors"]), _ptr(work["points"]), cap,
+                                       _stream())
+    _lib.check(st, "psam_surface_points")
+    return work
+
+
+def surface_dist(work, spacing=(1.0, 1.0, 1.0), keys=False):
+    """For every filled point of `work` (surface_points) the squared distance to the nearest point of the other surface of its row
+    (psam_surface_dist): the fp32 minimum of ((dx*sx)*(dx*sx) + (dy*sy)*(dy*sy)) + (dz*sz)*(dz*sz) over that segment, every
+    operation rounded separately (no FMA) on exact integer offsets, spacing (sz, sy, sx) rounded to fp32; +inf where the other
+    surface is empty. -> d2 fp32 [cap] (positions outside the filled segments hold +inf); keys=True also leaves
+    work["keys"] int64 [cap] = segment << 32 | bits of d2 (the largest int64 outside the segments). Asynchronous."""
+    sz, sy, sx = _surface_spacing(spacing)
+    cap, dev = work["cap"], work["points"].device
+    d2 = torch.full((cap,), float("inf"), dtype=torch.float32, device=dev)
+    kt = torch.full((cap,), 0x7fffffffffffffff, dtype=torch.int64, device=dev) if keys else None
+    st = _lib.lib().psam_surface_dist(_ptr(work["points"]), _ptr(work["offsets"]), _ptr(work["tiles"]), work["n"], work["H"],
+                                     work["W"], work["max_depth"], sz, sy, sx, cap, _ptr(d2), _ptr(kt), _stream())
+    _lib.check(st, "psam_surface_dist")
+    work["d2"], work["keys"] = d2, kt
+    return d2
+
+
+def surface_stats(sorted_d2, work, out=None):
+    """The table of psam_surface_stats from the d2 of every segment sorted ascending: sorted_d2 fp32 [>= filled points], or the
+    sorted int64 keys of surface_dist(keys=True). -> out float64 [n, 8], columns SURF_COLS: n_pred, n_gt (surface sizes), hd (the
+    larger directed maximum), hd95 (numpy.percentile(both directed sets together, 95), linear interpolation), assd (mean of the
+    two directed means), asd_pg, asd_gp (directed means, prediction to ground truth and back), status - float64 functions of
+    sqrt((double)d2), the sums in a fixed order (the same bits run to run and for any cap that fits). The five metrics are NaN where
+    a surface is empty (MedPy raises there) or the row was not filled. Asynchronous."""
+    if sorted_d2.dtype not in (torch.float32, torch.int64):
+        raise TypeError(f"sorted_d2: expected float32 values or int64 keys, got {sorted_d2.dtype}")
+    _req(sorted_d2, sorted_d2.dtype, "sorted_d2")
+    n = work["n"]
+    if sorted_d2.dim() != 1 or sorted_d2.numel() < work["cap"]:
+        raise ValueError(f"sorted_d2: expected [{work['cap']}] values, got {tuple(sorted_d2.shape)}")
+    if out is None:
+        out = torch.empty((n, 8), dtype=torch.float64, device=sorted_d2.device)
+    _req(out, torch.float64, "out")
+    assert out.is_contiguous() and out.numel() >= n * 8
+    st = _lib.lib().psam_surface_stats(_ptr(sorted_d2), 2 if sorted_d2.dtype == torch.int64 else 1, _ptr(work["counts"]),
+                                      _ptr(work["offsets"]), _ptr(work["status"]), n, _ptr(out), _stream())
+    _lib.check(st, "psam_surface_stats")
+    return out
+
+
+def surface_distances(pred, label, rows, spacing=(1.0, 1.0, 1.0), cap=None, out=None, max_depth=None):
+    """HD, HD95 and ASSD of every row, on the device: surface_points, surface_dist, ONE torch.sort of the int64 keys (non-negative
+    fp32 values order as their bit patterns) and surface_stats, all enqueued on the current stream; nothing comes to the host.
+    cap: the pool of surface points shared by the rows of the call; default surface_default_cap(voxels the rows cover) (rows on the
+    device: n * max_depth * H * W). Rows that do not fit are flagged SURFACE_OVERFLOW in the status column with their true counts
+    (metrics.surface_table recomputes exactly those). -> out float64 [n, 8] (SURF_COLS)."""
+    _surface_spacing(spacing)
+    if cap is None:
+        if isinstance(rows, torch.Tensor):
+            if max_depth is None:
+                raise ValueError("rows on the device: max_depth= must be given (the launch is sized from it)")
+            covered = rows.shape[0] * int(max_depth) * int(pred.shape[-2]) * int(pred.shape[-1])
+        else:
+            import numpy as np
+            r = np.asarray(rows, dtype=np.int64)
+            covered = int(r.reshape(-1, 5)[:, 4].clip(min=0).sum()) * int(pred.shape[-2]) * int(pred.shape[-1]) if r.size else 0
+        cap = surface_default_cap(covered)
+    work = surface_points(pred, label, rows, cap, max_depth=max_depth)
+    surface_dist(work, spacing, keys=True)
+    return surface_stats(torch.sort(work["keys"])[0], work, out=out)
+
+
 def normalize_chw(x, mean3, std3, out=None):
     """(x - mean[c]) / std[c] on [B,3,H,W]; x uint8 or fp32."""
     import ctypes

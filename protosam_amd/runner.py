@@ -11,7 +11,7 @@ import torch
 import torch.distributed as dist
 
 from .grid_proto_fewshot import FewShotSeg
-from .metrics import class_rows
+from .metrics import class_rows, surface_rows
 from .protosam import ALPNetWrapper, InputFactory, ProtoSAM, TYPE_ALPNET
 from .synth import synth_state_dict
 
@@ -257,51 +257,95 @@ def _slices_class_supports_loop(model, vol, supports, part_table, zs, batch, out
 
 
 # ---- evaluation: score every batch where it lies; only a [rows, 12] table is kept --------------------------
-def _scoring(labels, zs, classes, keep, batch, shape, device, label_value=1):
-    """table, batch buffer and sink of the evaluate_* functions. shape: of one slice's masks ([C, S, S] or [S, S])."""
+def _scoring(labels, zs, classes, keep, batch, shape, device, label_value=1, surface=None):
+    """table, batch buffer and sink of the evaluate_* functions. shape: of one slice's masks ([C, S, S] or [S, S]).
+    surface: None, or dict(spacing=(sy, sx) or (sz, sy, sx), cap=None): the sink also fills a per-slice surface table float64
+    [rows, 8] (ops.SURF_COLS) with one `ops.surface_distances` per batch; it is the fourth value returned (None without)."""
     from . import ops
     per = 1 if classes is None else len(classes)
     table = torch.empty((len(zs) * per, 12), dtype=torch.int64, device=device)
     if keep is not None:
         assert tuple(keep.shape) == (len(zs),) + tuple(shape) and keep.dtype == torch.uint8 and keep.is_contiguous()
     buf = None if keep is not None else torch.empty((min(batch, len(zs)),) + tuple(shape), dtype=torch.uint8, device=device)
+    surf = None
+    if surface is not None:
+        spacing, cap = ops._surface_spacing(surface["spacing"]), surface.get("cap")
+        surf = torch.empty((len(zs) * per, 8), dtype=torch.float64, device=device)
 
     def sink(i, j, masks):
         rows = class_rows(j - i, classes, label_planes=zs[i:j], label_value=label_value)
         ops.seg_counts(masks, labels, rows.tolist(), out=table[i * per:j * per])
-    return table, buf, sink
+        if surf is not None:
+            srows = surface_rows(j - i, classes, label_planes=zs[i:j], label_value=label_value)
+            ops.surface_distances(masks, labels, srows.tolist(), spacing, cap=cap, out=surf[i * per:j * per])
+    return table, buf, sink, surf
+
+
+def _with_surface(table, stats, surf):
+    """the return value of the evaluate_slices* functions: as it always was without surface=, the surface table appended with it"""
+    return (table, stats) if surf is None else (table, stats, surf)
 
 
 @torch.no_grad()
-def evaluate_slices(model, vol, labels, sup_imgs, sup_masks, zs, device, batch=1, mix_parts=True, keep=None, label_value=1):
+def evaluate_slices(model, vol, labels, sup_imgs, sup_masks, zs, device, batch=1, mix_parts=True, keep=None, label_value=1,
+                    surface=None):
     """`run_slices` scored in place: the masks of each batch go to ONE reused batch-sized buffer and one `ops.seg_counts` compares
     them with `labels` [Z, S, S] (the scan's label volume on the device, true where == label_value). Returns the int64 table
     [len(zs), 12] (ops.SEG_COLS; still on the device, nothing synchronised) and the prompts per slice. keep= (uint8
-    [len(zs), S, S]) also receives the masks, as `run_slices(..., out=keep)`."""
+    [len(zs), S, S]) also receives the masks, as `run_slices(..., out=keep)`.
+    surface=dict(spacing=(sy, sx) or (sz, sy, sx)[, cap=]): a third value, the per-slice surface table float64 [len(zs), 8]
+    (ops.SURF_COLS: HD, HD95, ASSD of every slice, `metrics.score_surfaces` reads it), filled batch by batch beside the counts; the
+    default changes nothing."""
     S = vol.shape[-1]
-    table, buf, sink = _scoring(labels, list(zs), None, keep, batch, (S, S), device, label_value)
-    return table, _slices_loop(model, vol, sup_imgs, sup_masks, zs, device, keep, buf, batch, mix_parts, sink)
+    table, buf, sink, surf = _scoring(labels, list(zs), None, keep, batch, (S, S), device, label_value, surface)
+    return _with_surface(table, _slices_loop(model, vol, sup_imgs, sup_masks, zs, device, keep, buf, batch, mix_parts, sink), surf)
 
 
 @torch.no_grad()
-def evaluate_slices_classes(model, vol, labels, sup_imgs, sup_masks_per_part, zs, classes, device, batch=16, keep=None):
+def evaluate_slices_classes(model, vol, labels, sup_imgs, sup_masks_per_part, zs, classes, device, batch=16, keep=None,
+                            surface=None):
     """`run_slices_classes` scored in place against the label volume `labels` [Z, S, S]: class c of the call is organ classes[c].
     One reused [batch, C, S, S] buffer, one `ops.seg_counts` per model call. Returns the int64 table [len(zs) * C, 12] (row
     k * C + c = slice zs[k], class c; on the device) and the prompted classes per slice. keep= (uint8 [len(zs), C, S, S]) also
-    receives the masks."""
+    receives the masks. surface= as `evaluate_slices`: a third value, the surface table float64 [len(zs) * C, 8], rows as the counts."""
     S, C = vol.shape[-1], len(classes)
     assert C == len(sup_masks_per_part[0])
-    table, buf, sink = _scoring(labels, list(zs), classes, keep, batch, (C, S, S), device)
-    return table, _slices_classes_loop(model, vol, sup_imgs, sup_masks_per_part, zs, device, batch, keep, buf, sink)
+    table, buf, sink, surf = _scoring(labels, list(zs), classes, keep, batch, (C, S, S), device, surface=surface)
+    return _with_surface(table, _slices_classes_loop(model, vol, sup_imgs, sup_masks_per_part, zs, device, batch, keep, buf, sink),
+                         surf)
 
 
 @torch.no_grad()
-def evaluate_slices_class_supports(model, vol, labels, supports, part_table, zs, classes, batch=16, keep=None):
-    """`run_slices_class_supports` scored in place; table, counts and keep= as `evaluate_slices_classes`."""
+def evaluate_slices_class_supports(model, vol, labels, supports, part_table, zs, classes, batch=16, keep=None, surface=None):
+    """`run_slices_class_supports` scored in place; table, counts, keep= and surface= as `evaluate_slices_classes`."""
     S, C = vol.shape[-1], len(classes)
     assert C == len(supports)
-    table, buf, sink = _scoring(labels, list(zs), classes, keep, batch, (C, S, S), vol.device)
-    return table, _slices_class_supports_loop(model, vol, supports, part_table, zs, batch, keep, buf, sink)
+    table, buf, sink, surf = _scoring(labels, list(zs), classes, keep, batch, (C, S, S), vol.device, surface=surface)
+    return _with_surface(table, _slices_class_supports_loop(model, vol, supports, part_table, zs, batch, keep, buf, sink), surf)
+
+
+@torch.no_grad()
+def score_scan_surfaces(keep, labels, classes, spacing, zs=None, cap=None):
+    """The boundary measures of a whole scan in 3-D: keep uint8 [Z, C, S, S] (the masks evaluate_slices_classes(..., keep=) left; [Z,
+    S, S] with classes = None: one class, true where labels == 1) against the label volume `labels` [Z', S, S]; slice k of keep is
+    label plane zs[k] (default k). One row per class over the kept volume with depth Z (6-neighbour surfaces, the first and last
+    kept slice count as the volume's faces), spacing (sz, sy, sx) as slice_io.read_nifti's header gives it. One launch chain for
+    all classes; rows that overflow the default pool are recomputed (`metrics.surface_table`).
+    -> float64 array [C, 8] on the host (ops.SURF_COLS; `metrics.score_surfaces` reads it). It synchronises."""
+    from .metrics import surface_table
+    Z = keep.shape[0]
+    if keep.dim() != (3 if classes is None else 4) or (classes is not None and keep.shape[1] != len(classes)):
+        raise ValueError(f"keep {tuple(keep.shape)} does not hold {None if classes is None else len(classes)} classes per slice")
+    vol = (keep[None] if keep.dim() == 3 else keep.permute(1, 0, 2, 3)).contiguous()          # class-major volumes
+    zs = list(range(Z)) if zs is None else [int(z) for z in zs]
+    if len(zs) != Z:
+        raise ValueError(f"zs has {len(zs)} entries for {Z} kept slices")
+    if zs == list(range(zs[0], zs[0] + Z)):
+        lab, first = labels, zs[0]
+    else:
+        lab, first = labels[torch.tensor(zs, device=labels.device)], 0
+    rows = surface_rows(1, classes, label_planes=[first], depth=Z)
+    return surface_table(vol.reshape((-1,) + tuple(vol.shape[-2:])), lab, rows.tolist(), spacing, cap=cap)
 
 
 # ---- image sets (image_io.ImageSet): the polyp branch of validation_protosam.py:307-449 -----------------------------------------
@@ -347,13 +391,15 @@ def _images_loop(model, image_set, support, indices, batch, out, buf, sink):
 
 
 @torch.no_grad()
-def evaluate_images(model, image_set, support, indices, batch=4, keep=None, skip_no_organ_slices=True):
+def evaluate_images(model, image_set, support, indices, batch=4, keep=None, skip_no_organ_slices=True, surface=None):
     """`run_images` scored where each batch lies: one `ops.seg_counts` per batch against the batch's own labels, then
     `metrics.score_slices` on the table with the per-image confidences and cases. -> its dict (dice / iou / precision / recall, their
     means, per-case means, "bboxes_w_scores" for `metrics.eval_detection`) plus "table" (int64 [n, 12], host) and "n_prompts".
-    keep= (uint8 [len(indices), S, S]) also receives the masks."""
+    keep= (uint8 [len(indices), S, S]) also receives the masks.
+    surface=dict(spacing=(sy, sx)[, cap=]): also "surface_table" (float64 [n, 8], host, ops.SURF_COLS: HD, HD95, ASSD per image) and
+    "surface" (`metrics.score_surfaces` of it with the cases); the default leaves the dict as it was."""
     from . import ops
-    from .metrics import score_slices
+    from .metrics import score_slices, score_surfaces
     indices = list(indices)
     S, dev = image_set.S, image_set.device
     table = torch.empty((len(indices), 12), dtype=torch.int64, device=dev)
@@ -361,12 +407,22 @@ def evaluate_images(model, image_set, support, indices, batch=4, keep=None, skip
         assert tuple(keep.shape) == (len(indices), S, S) and keep.dtype == torch.uint8 and keep.is_contiguous()
     buf = None if keep is not None else torch.empty((min(max(int(batch), 1), len(indices)), S, S), dtype=torch.uint8, device=dev)
 
+    surf = None
+    if surface is not None:
+        spacing, cap = ops._surface_spacing(surface["spacing"]), surface.get("cap")
+        surf = torch.empty((len(indices), 8), dtype=torch.float64, device=dev)
+
     def sink(i, j, masks, labels):
         ops.seg_counts(masks, labels, class_rows(j - i).tolist(), out=table[i:j])
+        if surf is not None:
+            ops.surface_distances(masks, labels, surface_rows(j - i).tolist(), spacing, cap=cap, out=surf[i:j])
     stats, scores, cases = _images_loop(model, image_set, support, indices, batch, keep, buf, sink)
     host = table.cpu().numpy()
     res = score_slices(host, scores=scores, cases=cases, skip_no_organ_slices=skip_no_organ_slices)
     res["table"], res["n_prompts"] = host, stats
+    if surf is not None:
+        res["surface_table"] = surf.cpu().numpy()
+        res["surface"] = score_surfaces(res["surface_table"], cases=cases)
     return res
 
 

@@ -144,6 +144,17 @@ def write_nifti(path, array_zyx, peeled_info=None):
         f.write(bytes(hdr) + b"\0\0\0\0" + a.tobytes())
 
 
+def slice_spacing(info, image_size):
+    """(sz, sy, sx) of the S x S slices of a `ScanSlices` in the header's units: the voxel spacing of `read_nifti(peel_info=True)`
+    (stored x, y, z) with the in-plane steps scaled by the resize from the file's [H, W] to image_size. (1, 1, 1) without a header.
+    This is the `spacing` of ops.surface_distances / runner.score_scan_surfaces."""
+    if info is None:
+        return (1.0, 1.0, 1.0)
+    sx, sy, sz = (float(v) for v in info["spacing"])
+    _, H, W = info["array_size"]
+    return (sz, sy * H / float(image_size), sx * W / float(image_size))
+
+
 class ScanSlices:
     """A scan on the device, ready for the per-slice loop: `images` fp32 [Z, tile, S, S] and (optionally) `labels` fp32
     [Z, S, S], built from the raw voxel arrays by the two HIP kernels."""

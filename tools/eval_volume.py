@@ -6,6 +6,8 @@ ScanSlices -> class_part_table / class_support_slices -> evaluate_slices_class_s
 
 Weights are the seeded synthetic ones of `runner.build_protosam` (`--sam-depth` / `--dino-depth` cut the encoders for a quick
 run). Prints one JSON line: per-class scan-level Dice (`Metric.get_mDice`), the per-slice means of `score_slices`, slices per second.
+`--surface` adds the boundary measures per organ beside Dice: scan-level HD95 and ASSD in 3-D (`runner.score_scan_surfaces` on the
+kept masks) and their per-slice means, in the units of the NIfTI header's voxel spacing (`ScanSlices.info`; 1 for synthetic scans).
 """
 import argparse
 import json
@@ -40,12 +42,13 @@ def main():
     ap.add_argument("--sam-type", default="vit_b")
     ap.add_argument("--sam-depth", type=int, default=None)
     ap.add_argument("--dino-depth", type=int, default=None)
+    ap.add_argument("--surface", action="store_true", help="also HD95 and ASSD per organ (spacing from the NIfTI header)")
     args = ap.parse_args()
     import numpy as np
     import torch
     from protosam_amd import metrics, runner
     from protosam_amd.protosam import InputFactory, TYPE_ALPNET
-    from protosam_amd.slice_io import ScanSlices
+    from protosam_amd.slice_io import ScanSlices, slice_spacing
     if not torch.cuda.is_available():
         raise SystemExit("eval_volume.py runs the GPU pipeline: no device found")
     dev = torch.device("cuda:0")
@@ -74,11 +77,28 @@ def main():
     zs = list(range(vol.shape[0]))
     runner.evaluate_slices_class_supports(model, vol, labels, supports, part_table, zs[:args.batch], classes, batch=args.batch)   # warm
     torch.cuda.synchronize()
+    C = len(classes)
+    spacing = slice_spacing(qry.info, S)
+    keep = torch.empty((len(zs), C, S, S), dtype=torch.uint8, device=dev) if args.surface else None
     t0 = time.perf_counter()
-    table, prompted = runner.evaluate_slices_class_supports(model, vol, labels, supports, part_table, zs, classes, batch=args.batch)
+    res = runner.evaluate_slices_class_supports(model, vol, labels, supports, part_table, zs, classes, batch=args.batch, keep=keep,
+                                                surface=dict(spacing=spacing) if args.surface else None)
+    table, prompted = res[0], res[1]
     host = table.cpu().numpy()                                    # the one copy of the scan: 96 bytes per (slice, class)
     dt = time.perf_counter() - t0
-    C = len(classes)
+    extra = {}
+    if args.surface:
+        nan_to_none = lambda v: None if v != v else float(v)      # noqa: E731  (JSON has no NaN)
+        per_slice = metrics.score_surfaces(metrics.surface_table(keep, labels, metrics.surface_rows(len(zs), classes).tolist(),
+                                                                 spacing, table=res[2]),
+                                           cases=[f"class{classes[r % C]}" for r in range(len(host))])
+        scan = runner.score_scan_surfaces(keep, labels, classes, spacing)
+        extra = {"spacing_zyx": list(spacing), "scan_hd95_per_class": [nan_to_none(v) for v in scan[:, metrics.HD95]],
+                 "scan_assd_per_class": [nan_to_none(v) for v in scan[:, metrics.ASSD]],
+                 "scan_hd_per_class": [nan_to_none(v) for v in scan[:, metrics.HD]],
+                 "slice_mean_hd95_per_class": per_slice["hd95_cases"], "slice_mean_assd_per_class": per_slice["assd_cases"],
+                 "surface_rows_scored": len(per_slice["rows"]), "surface_rows_empty_pred": len(per_slice["empty_pred"]),
+                 "surface_rows_empty_gt": len(per_slice["empty_gt"])}
     m = metrics.Metric(max_label=max(classes))
     for k in range(len(zs)):
         for c, cls in enumerate(classes):
@@ -90,7 +110,7 @@ def main():
     print(json.dumps({"classes": classes, "scan_dice_per_class": [float(v) for v in dice_cls], "scan_dice_mean": float(dice_mean),
                       "slices": len(zs), "rows_scored": len(sc["rows"]), "slice_mean_dice": sc["mean_dice"], "slice_mean_iou": sc["mean_iou"],
                       "slice_mean_dice_per_class": sc["dice_cases"], "prompted_pairs": int(sum(prompted)),
-                      "slices_per_s": len(zs) / dt}))
+                      "slices_per_s": len(zs) / dt, **extra}))
 
 
 if __name__ == "__main__":
