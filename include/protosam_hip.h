@@ -582,6 +582,28 @@ int psam_small_regions_workspace(int H, int W, int chunk, long long* bytes);
 int psam_small_regions(const void* masks, int m, int H, int W, double area_thresh, int chunk, void* out, int* boxes, float* scores,
                        int* info, void* scratch, long long scratch_bytes, void* stream);
 
+/* ---- connected-component clean-up of binary volumes (csrc/volume_regions.hip) -----------------------------------------------
+ * R volumes of D x H x W uint8 voxels (non-0 = set); voxel (r, z, y, x) of `vol` and of `out` lies at
+ * base + r * stride_r + z * stride_z + y * W + x: a class-major [R,D,H,W] buffer has stride_r = D*H*W, stride_z = H*W, a
+ * slice-major [Z,C,S,S] buffer of kept masks is cleaned where it lies with stride_r = S*S, stride_z = C*S*S.
+ * connectivity 6 / 18 / 26 = face, face + edge, face + edge + corner neighbours (scipy's generate_binary_structure(3, 1 | 2 | 3);
+ * with D == 1 they are 4 / 8 / 8 in the plane). Every component with size < min_voxels is dropped; keep_largest = 1 keeps only
+ * the largest survivor, among equally large ones the one whose first voxel comes first in raster order (z, y, x). A min_voxels
+ * above every size leaves `out` empty (psam_small_regions keeps the largest island in that case; this entry does not).
+ * out uint8 {0, 1}, same geometry as vol; out == vol is allowed. info int64 [R,12] = components found, components kept, voxels
+ * in, voxels out, size of the input's largest component, its root as (z * H + y) * W + x (-1 for an empty volume), the box of
+ * out z0, y0, x0, z1, y1, x1 inclusive (all -1 for an empty out). labels (NULL skips it) int32 [R,D,H,W] contiguous: 0 for
+ * background, the input's components before any filtering numbered 1..n per volume in the raster order of their first voxel
+ * (scipy.ndimage.label's numbering), by a two-level prefix count of the roots: no limit on their number.
+ * The R volumes are walked in chunks of `chunk` (<= 65535 per launch), every launch enqueued on `stream`, no host wait. scratch,
+ * 8-byte aligned, holds a chunk: chunk * (8 * D*H*W + 64 + (labels ? 4 * ceil(D*H*W / 256) : 0)) bytes.
+ * Status 1 before any launch: R < 0, D, H or W <= 0, D*H*W >= 2^31 (or D * H * (W rounded up to 256) beyond 2^32 - 1), chunk < 1,
+ * connectivity not 6 / 18 / 26, min_voxels < 0, keep_largest not 0 / 1, a stride below H*W, and with R > 0 a NULL vol, out, info
+ * or scratch, misaligned or short scratch. R == 0 does nothing and returns 0. */
+int psam_volume_regions(const void* vol, int R, int D, int H, int W, long long stride_r, long long stride_z, int connectivity,
+                        long long min_voxels, int keep_largest, int chunk, void* out, long long* info, int* labels, void* scratch,
+                        long long scratch_bytes, void* stream);
+
 /* Slice hand-off from a scan volume (raw NIfTI voxels [Z,H,W]; vol_dtype 0 int16, 1 float32, 2 uint8, 3 int32).
  * psam_volume_stats: out[0] = sum(x), out[1] = sum(x^2) in fp64, x = voxel*slope + inter  (MR_normalize / get_CT_statistics,
  *   dataloaders/dataset_utils.py:76-108).

@@ -107,6 +107,8 @@ SIGNATURES = {
     "psam_small_regions_workspace": [c_int, c_int, c_int, ctypes.POINTER(c_longlong)],
     "psam_small_regions": [c_void_p, c_int, c_int, c_int, ctypes.c_double, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                            c_longlong, c_void_p],
+    "psam_volume_regions": [c_void_p, c_int, c_int, c_int, c_int, c_longlong, c_longlong, c_int, c_longlong, c_int, c_int, c_void_p,
+                            c_void_p, c_void_p, c_void_p, c_longlong, c_void_p],
     "psam_mask_counts": [c_void_p, c_int, c_void_p, c_int, c_void_p] + [c_int] * 6 + [c_float, c_void_p, c_void_p, c_void_p],
     "psam_best_iou": [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p],
     "psam_mask_downscale": [c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p],

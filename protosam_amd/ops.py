@@ -1606,6 +1606,129 @@ def small_regions_table(table, m):
     return (table[1:1 + count].astype("int64"), table[1 + m:1 + 5 * m].reshape(m, 4), table[1 + 5 * m:1 + 9 * m].reshape(m, 4))
 
 
+# ---- connected-component clean-up of volumes (csrc/volume_regions.hip) --------------------------------------
+VOLUME_REGIONS_BUDGET = 1 << 30    # bytes of scratch volume_regions sizes its chunk for (8 bytes per voxel and volume in flight)
+VOLREG_COLS = ("components", "kept", "voxels_in", "voxels_out", "largest_size", "largest_root", "z0", "y0", "x0", "z1", "y1", "x1")
+_vr_scratch = {}
+
+
+def _volreg_shape(D, H, W):
+    D, H, W = int(D), int(H), int(W)
+    if D <= 0 or H <= 0 or W <= 0 or D * H * W >= 1 << 31 or D * H * ((W + 255) // 256) * 256 > 0xffffffff:
+        raise ValueError(f"volume: D, H and W must be positive with D * H * W below 2^31, got {D} x {H} x {W}")
+    return D, H, W
+
+
+def volume_regions_workspace(D, H, W, chunk, labels=False):
+    """Bytes of scratch psam_volume_regions needs for `chunk` volumes of D x H x W in flight: parent and size arrays, 64 bytes of
+    accumulators and, with labels, one int32 per 256-voxel block (the scan's block sums)."""
+    D, H, W = _volreg_shape(D, H, W)
+    if int(chunk) < 1:
+        raise ValueError(f"chunk must be at least 1, got {chunk}")
+    n = D * H * W
+    return int(chunk) * (8 * n + 64 + (4 * ((n + 255) // 256) if labels else 0))
+
+
+def volume_regions_chunk(R, D, H, W, budget=None):
+    """Volumes in flight for R volumes of D x H x W under a scratch budget in bytes (default VOLUME_REGIONS_BUDGET): at least one."""
+    budget = VOLUME_REGIONS_BUDGET if budget is None else int(budget)
+    return max(1, min(max(int(R), 1), budget // volume_regions_workspace(D, H, W, 1, labels=True)))
+
+
+def volume_regions(vol, connectivity=26, min_voxels=0, keep_largest=False, labels=False, out=None, chunk=None, scratch=None,
+                   layout="rdhw"):
+    """3-D connected components per volume and the clean-up on top of them (psam_volume_regions), nothing synchronised.
+    vol uint8 (0 / non-0): [D, H, W] (one volume), [R, D, H, W] (layout "rdhw", class-major) or the slice-major [Z, C, H, W] of
+    kept masks (layout "zchw": volume r is class r, read where it lies); [H, W] planes contiguous, outer strides free.
+    connectivity 6 / 18 / 26; components with size < min_voxels are dropped (all of them: then `out` is empty); keep_largest keeps
+    the largest survivor only, ties to the first in raster order.
+    -> (out, info[, labels]): out uint8 {0, 1} shaped and strided as vol (out= may be vol itself: in place); info int64 [R, 12]
+    (VOLREG_COLS; `volume_regions_table` reads a host copy); labels=True adds int32 [R, D, H, W] (contiguous and class-major for
+    either layout, [D, H, W] for a 3-D vol): the input's components numbered as scipy.ndimage.label numbers them, or pass an int32
+    tensor of that shape to fill. `chunk`: volumes in flight (default: what fits VOLUME_REGIONS_BUDGET, at least one); `scratch`:
+    int64 device tensor of volume_regions_workspace bytes (default: cached per shape)."""
+    if vol is None or not torch.is_tensor(vol):
+        raise TypeError("vol: expected a tensor")
+    if vol.dtype != torch.uint8:
+        raise TypeError(f"vol: expected {torch.uint8}, got {vol.dtype}")
+    if layout not in ("rdhw", "zchw"):
+        raise ValueError(f"layout must be 'rdhw' or 'zchw', got {layout!r}")
+    if int(connectivity) not in (6, 18, 26) or connectivity != int(connectivity):
+        raise ValueError(f"connectivity must be 6, 18 or 26, got {connectivity}")
+    if min_voxels != int(min_voxels) or int(min_voxels) < 0:
+        raise ValueError(f"min_voxels must be a non-negative integer, got {min_voxels}")
+    if keep_largest not in (0, 1, False, True):
+        raise ValueError(f"keep_largest must be 0 or 1, got {keep_largest}")
+    if vol.dim() == 3 and layout == "rdhw":
+        R, (D, H, W), sr, sz = 1, vol.shape, None, vol.stride(0)
+    elif vol.dim() == 4 and layout == "rdhw":
+        (R, D, H, W), sr, sz = vol.shape, vol.stride(0), vol.stride(1)
+    elif vol.dim() == 4:
+        (D, R, H, W), sr, sz = vol.shape, vol.stride(1), vol.stride(0)
+    else:
+        raise ValueError(f"vol: expected [D, H, W], [R, D, H, W] or, with layout='zchw', [Z, C, H, W]; got {tuple(vol.shape)}")
+    D, H, W = _volreg_shape(D, H, W)
+    if R == 0:
+        raise ValueError(f"vol: no volume in {tuple(vol.shape)}")
+    if (W > 1 and vol.stride(-1) != 1) or (H > 1 and vol.stride(-2) != W):
+        raise ValueError(f"vol: [H, W] planes must be contiguous, got strides {tuple(vol.stride())}")
+    _req(vol, torch.uint8, "vol")
+    sr = D * H * W if sr is None or R == 1 and sr < H * W else sr
+    sz = H * W if D == 1 and sz < H * W else sz
+    if sr < H * W or sz < H * W:
+        raise ValueError(f"vol: planes overlap, strides {tuple(vol.stride())}")
+    if chunk is None:
+        chunk = volume_regions_chunk(R, D, H, W)
+    chunk = int(chunk)
+    if chunk < 1:
+        raise ValueError(f"chunk must be at least 1, got {chunk}")
+    dev = vol.device
+    if out is None:
+        out = torch.empty_strided(tuple(vol.shape), tuple(vol.stride()), dtype=torch.uint8, device=dev)
+    _req(out, torch.uint8, "out")
+    if tuple(out.shape) != tuple(vol.shape) or tuple(out.stride()) != tuple(vol.stride()):
+        raise ValueError(f"out: expected shape {tuple(vol.shape)} and strides {tuple(vol.stride())}, got {tuple(out.shape)} and "
+                         f"{tuple(out.stride())}")
+    lab_shape = (D, H, W) if vol.dim() == 3 else (R, D, H, W)
+    lab = None
+    if torch.is_tensor(labels):
+        lab = labels
+        _req(lab, torch.int32, "labels")
+        if tuple(lab.shape) != lab_shape or not lab.is_contiguous():
+            raise ValueError(f"labels: expected a contiguous {lab_shape}, got {tuple(lab.shape)}")
+    elif labels:
+        lab = torch.empty(lab_shape, dtype=torch.int32, device=dev)
+    need = volume_regions_workspace(D, H, W, chunk, labels=lab is not None)
+    if scratch is None:
+        key = (str(dev), D, H, W, chunk, lab is not None)
+        if key not in _vr_scratch:
+            _vr_scratch.clear()                      # (one working set at a time: it is sized by a byte budget)
+            _vr_scratch[key] = torch.empty(((need + 7) // 8,), dtype=torch.int64, device=dev)
+        scratch = _vr_scratch[key]
+    if not torch.is_tensor(scratch) or not scratch.is_cuda or scratch.dtype != torch.int64 or not scratch.is_contiguous():
+        raise TypeError("scratch: expected a contiguous int64 device tensor")
+    if scratch.numel() * 8 < need:
+        raise ValueError(f"scratch: {scratch.numel() * 8} bytes, {need} needed for {chunk} volumes of {D} x {H} x {W} in flight")
+    info = torch.empty((R, 12), dtype=torch.int64, device=dev)
+    st = _lib.lib().psam_volume_regions(_ptr(vol), R, D, H, W, sr, sz, int(connectivity), int(min_voxels), int(keep_largest), chunk,
+                                        _ptr(out), _ptr(info), _ptr(lab), _ptr(scratch), scratch.numel() * 8, _stream())
+    _lib.check(st, "psam_volume_regions")
+    return (out, info) if lab is None else (out, info, lab)
+
+
+def volume_regions_table(info):
+    """The `info` of volume_regions (device or host) -> one dict per volume, keyed by VOLREG_COLS, plus "voxels_dropped" and "box"
+    (z0, y0, x0, z1, y1, x1, or None for an empty result). A device tensor is copied, which waits for the stream."""
+    host = info.detach().cpu().numpy() if torch.is_tensor(info) else info
+    rows = []
+    for r in host.reshape(-1, len(VOLREG_COLS)).tolist():
+        d = dict(zip(VOLREG_COLS, (int(v) for v in r)))
+        d["voxels_dropped"] = d["voxels_in"] - d["voxels_out"]
+        d["box"] = None if d["voxels_out"] == 0 else tuple(int(v) for v in r[6:12])
+        rows.append(d)
+    return rows
+
+
 def mask_counts(low, records, count, MID, H, W, variant, label, thr=0.0, counts=None):
     """int64 [cap,3] {tp, fp, fn} against `label` uint8 [H,W] of the first min(count, cap) records of ONE group (records int32
     [cap,AMG_REC], count int32 [1], both on the device, as amg_select leaves them): mask_binarize's counts without the masks and

@@ -348,6 +348,43 @@ def score_scan_surfaces(keep, labels, classes, spacing, zs=None, cap=None):
     return surface_table(vol.reshape((-1,) + tuple(vol.shape[-2:])), lab, rows.tolist(), spacing, cap=cap)
 
 
+def _kept_classes(keep, classes):
+    if keep.dim() != (3 if classes is None else 4) or (classes is not None and keep.shape[1] != len(classes)):
+        raise ValueError(f"keep {tuple(keep.shape)} does not hold {None if classes is None else len(classes)} classes per slice")
+
+
+@torch.no_grad()
+def clean_scan(keep, classes=None, connectivity=26, min_voxels=0, keep_largest=True, out=None):
+    """The connected-component clean-up of a kept scan in 3-D, per class, on the device (`ops.volume_regions`): keep uint8 [Z, C,
+    S, S] as evaluate_slices_classes(..., keep=) left it (read where it lies, no class-major copy), or [Z, S, S] with classes =
+    None. Every component (connectivity 6 / 18 / 26) below min_voxels voxels is dropped; keep_largest keeps only the largest
+    survivor of each class, ties to the first in raster order. out=keep cleans in place.
+    -> (cleaned uint8 shaped as keep, info int64 [C, 12] on the device: ops.VOLREG_COLS, `ops.volume_regions_table` reads it).
+    Nothing is synchronised."""
+    from . import ops
+    _kept_classes(keep, classes)
+    return ops.volume_regions(keep, connectivity=connectivity, min_voxels=min_voxels, keep_largest=keep_largest, out=out,
+                              layout="rdhw" if keep.dim() == 3 else "zchw")
+
+
+@torch.no_grad()
+def score_scan(keep, labels, classes, zs=None):
+    """The scan-level counts of kept (or cleaned) masks: keep uint8 [Z, C, S, S] ([Z, S, S] with classes = None: one class, true
+    where labels == 1) against the label volume `labels` [Z', S, S]; slice k of keep is label plane zs[k] (default k). One
+    `ops.seg_counts` over every (slice, class), reduced over the slices on the device: counts summed, boxes united.
+    -> int64 [C, 12] (ops.SEG_COLS; an empty box is (INT32_MAX, INT32_MAX, -1, -1) as seg_counts leaves it), on the device,
+    nothing synchronised."""
+    from . import ops
+    _kept_classes(keep, classes)
+    Z = keep.shape[0]
+    zs = list(range(Z)) if zs is None else [int(z) for z in zs]
+    if len(zs) != Z:
+        raise ValueError(f"zs has {len(zs)} entries for {Z} kept slices")
+    per = ops.seg_counts(keep, labels, class_rows(Z, classes, label_planes=zs).tolist()).view(Z, -1, 12)
+    lo, hi = per.amin(dim=0), per.amax(dim=0)
+    return torch.cat([per[..., :4].sum(dim=0), lo[:, 4:6], hi[:, 6:8], lo[:, 8:10], hi[:, 10:12]], dim=1)
+
+
 # ---- image sets (image_io.ImageSet): the polyp branch of validation_protosam.py:307-449 -----------------------------------------
 @torch.no_grad()
 def run_images(model, image_set, support, indices, batch=4, out=None):

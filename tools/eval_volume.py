@@ -8,6 +8,9 @@ Weights are the seeded synthetic ones of `runner.build_protosam` (`--sam-depth` 
 run). Prints one JSON line: per-class scan-level Dice (`Metric.get_mDice`), the per-slice means of `score_slices`, slices per second.
 `--surface` adds the boundary measures per organ beside Dice: scan-level HD95 and ASSD in 3-D (`runner.score_scan_surfaces` on the
 kept masks) and their per-slice means, in the units of the NIfTI header's voxel spacing (`ScanSlices.info`; 1 for synthetic scans).
+`--clean largest|min` (`--connectivity`, `--min-voxels`) also scores the scan after the 3-D connected-component clean-up of
+`runner.clean_scan`: `scan_dice_per_class_clean`, `components_per_class`, `voxels_dropped_per_class` and, with `--surface`, the
+`scan_*_per_class_clean` boundary measures.
 """
 import argparse
 import json
@@ -43,6 +46,11 @@ def main():
     ap.add_argument("--sam-depth", type=int, default=None)
     ap.add_argument("--dino-depth", type=int, default=None)
     ap.add_argument("--surface", action="store_true", help="also HD95 and ASSD per organ (spacing from the NIfTI header)")
+    ap.add_argument("--clean", choices=("largest", "min"), default=None,
+                    help="also score the scan after a 3-D connected-component clean-up per organ: keep the largest component, or "
+                         "drop the components below --min-voxels")
+    ap.add_argument("--connectivity", type=int, choices=(6, 18, 26), default=26)
+    ap.add_argument("--min-voxels", type=int, default=0, help="components below this many voxels are dropped (with either --clean)")
     args = ap.parse_args()
     import numpy as np
     import torch
@@ -79,7 +87,7 @@ def main():
     torch.cuda.synchronize()
     C = len(classes)
     spacing = slice_spacing(qry.info, S)
-    keep = torch.empty((len(zs), C, S, S), dtype=torch.uint8, device=dev) if args.surface else None
+    keep = torch.empty((len(zs), C, S, S), dtype=torch.uint8, device=dev) if args.surface or args.clean else None
     t0 = time.perf_counter()
     res = runner.evaluate_slices_class_supports(model, vol, labels, supports, part_table, zs, classes, batch=args.batch, keep=keep,
                                                 surface=dict(spacing=spacing) if args.surface else None)
@@ -87,8 +95,8 @@ def main():
     host = table.cpu().numpy()                                    # the one copy of the scan: 96 bytes per (slice, class)
     dt = time.perf_counter() - t0
     extra = {}
+    nan_to_none = lambda v: None if v != v else float(v)          # noqa: E731  (JSON has no NaN)
     if args.surface:
-        nan_to_none = lambda v: None if v != v else float(v)      # noqa: E731  (JSON has no NaN)
         per_slice = metrics.score_surfaces(metrics.surface_table(keep, labels, metrics.surface_rows(len(zs), classes).tolist(),
                                                                  spacing, table=res[2]),
                                            cases=[f"class{classes[r % C]}" for r in range(len(host))])
@@ -99,6 +107,27 @@ def main():
                  "slice_mean_hd95_per_class": per_slice["hd95_cases"], "slice_mean_assd_per_class": per_slice["assd_cases"],
                  "surface_rows_scored": len(per_slice["rows"]), "surface_rows_empty_pred": len(per_slice["empty_pred"]),
                  "surface_rows_empty_gt": len(per_slice["empty_gt"])}
+    if args.clean:
+        # the kept masks cleaned where they lie, then one counts table and (with --surface) one surface table per organ
+        from protosam_amd import ops
+        cleaned, info = runner.clean_scan(keep, classes, connectivity=args.connectivity, min_voxels=args.min_voxels,
+                                          keep_largest=args.clean == "largest", out=keep)
+        scan_counts = runner.score_scan(cleaned, labels, classes).cpu().numpy()
+        mc = metrics.Metric(max_label=max(classes))
+        for c, cls in enumerate(classes):
+            tp, fp, fn, tn = scan_counts[c, :4]
+            mc.record_table(np.array([[tn, fn, fp], [tp, fp, fn]]), labels=[cls])
+        with np.errstate(all="ignore"):
+            dice_clean, _, _ = mc.get_mDice(labels=classes, n_scan=0)
+        regions = ops.volume_regions_table(info)
+        extra.update({"scan_dice_per_class_clean": [nan_to_none(v) for v in dice_clean],
+                      "components_per_class": [r["components"] for r in regions],
+                      "voxels_dropped_per_class": [r["voxels_dropped"] for r in regions]})
+        if args.surface:
+            scan = runner.score_scan_surfaces(cleaned, labels, classes, spacing)
+            extra.update({"scan_hd95_per_class_clean": [nan_to_none(v) for v in scan[:, metrics.HD95]],
+                          "scan_assd_per_class_clean": [nan_to_none(v) for v in scan[:, metrics.ASSD]],
+                          "scan_hd_per_class_clean": [nan_to_none(v) for v in scan[:, metrics.HD]]})
     m = metrics.Metric(max_label=max(classes))
     for k in range(len(zs)):
         for c, cls in enumerate(classes):
